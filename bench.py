@@ -7,9 +7,15 @@ random-init weights, bf16 dense compute, f16 embedding wire, Adagrad sparse
 optimizer, bounded-staleness async sparse pipeline + DDP dense.
 
 Contract (driver):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1 is launched via torch.distributed.run (one rank per GPU over RCCL);
 weak scaling (per-GPU batch fixed).  Rank 0 prints ONE json line.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, optionally dump the last step's outputs, print the result line.
+--full is reserved for measurements beyond the headline figure (baselines,
+other configurations, comparisons); there are none today, so it currently
+runs the same steps as a plain run.
 """
 import argparse
 import json
@@ -69,6 +75,14 @@ def parse_args():
                         "(beats the graphed hipBLASLt path since the "
                         "XOR-swizzled staging fixed wgrad; 0 = hipBLASLt; "
                         "preset-dependent default)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, logits, dense parameters and "
+                        "seeded samples of the embedding sums and their "
+                        "gradient) as DIR/<name>.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none today: same as a plain run)")
     args = p.parse_args()
     preset = dict(PRESETS[args.preset])
     preset.setdefault("batch_size", 8192)  # x8 ranks = the MLPerf DLRM 64k global batch
@@ -161,6 +175,9 @@ def main():
         device=device,
         dist_ctx=DistContext.new_sparse_group(),
     )
+    # same dense init on every run and rank (the host batches are seeded
+    # below): two builds given the same arguments see identical inputs
+    torch.manual_seed(1234)
     if args.model == "dlrm":
         model = DLRM(
             num_sparse=n_slots, num_dense=args.num_dense, dim=dim,
@@ -370,6 +387,7 @@ def main():
                 def iteration():
                     static["base"].grad.zero_()
                     logits = model(static["dense"], static["base"])
+                    static["logits"] = logits.detach()  # no autograd graph kept alive
                     loss = loss_fn(logits.float(), static["label"])
                     loss.backward()
                     with torch.no_grad():
@@ -403,6 +421,7 @@ def main():
                 def iteration():
                     static["base"].grad.zero_()
                     logits = model(static["dense"], static["base"])
+                    static["logits"] = logits.detach()  # no autograd graph kept alive
                     loss = loss_fn(logits.float(), static["label"])
                     loss.backward()
                     grads = [p.grad for p in g_params]
@@ -419,6 +438,7 @@ def main():
                     static["base"].grad.zero_()
                     with torch.autocast("cuda", dtype=amp_dtype, cache_enabled=False):
                         logits = model(static["dense"], static["base"])
+                        static["logits"] = logits.detach()  # no autograd graph kept alive
                         loss = loss_fn(logits.float(), static["label"])
                     loss.backward()
                     opt.step()
@@ -509,6 +529,8 @@ def main():
         ev_bwd = torch.cuda.Event()
         ev_staged = torch.cuda.Event()
 
+    last = {}  # what the most recent eager step produced (--dump-outputs)
+
     def train_step(tb):
         if graph is not None:
             if timing:
@@ -555,6 +577,7 @@ def main():
             embs = tb.training_embeddings()
             logits = model(tb.non_id_type_tensors, embs)
             loss = loss_fn(logits.float(), tb.label_tensors[0])
+        last["logits"], last["loss"] = logits.detach(), loss.detach()
         loss.backward()
         engine.apply_gradients_base(tb)
         opt.step()
@@ -608,6 +631,21 @@ def main():
         elapsed = float(t.item())
 
     pipeline.stop()
+    if args.dump_outputs and rank == 0:
+        if graph is not None:
+            out, base = static, static["base"]
+        else:
+            out, base = last, tb._groups[0].sum_base
+        _dump_outputs(
+            args.dump_outputs,
+            loss=out["loss"],
+            logits=out["logits"],
+            dense_params=torch.cat(
+                [p.detach().reshape(-1).float() for p in model.parameters()]
+            ),
+            emb_sum=base,
+            emb_sum_grad=None if base is None else base.grad,
+        )
     if world > 1:
         # the padded-a2a fast path drops keys to a dummy slot on bucket
         # overflow (probability ~exp(-20 sigma) with the default slack);
@@ -673,6 +711,28 @@ def main():
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array: 8 MB of float32, 5 arrays < 64 MB
+
+
+def _dump_outputs(dst, **arrays):
+    """Write each array as dst/<name>.npy in float32.  An array larger than
+    DUMP_MAX_ELEMS is reduced to a fixed sample of its flattened elements
+    (seeded by its size only, so two builds pick the same elements)."""
+    os.makedirs(dst, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(
+                np.random.default_rng(flat.numel()).integers(
+                    0, flat.numel(), size=DUMP_MAX_ELEMS
+                )
+            )
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(dst, name + ".npy"), flat.float().cpu().numpy())
 
 
 class _nullcontext:

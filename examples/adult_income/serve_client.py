@@ -49,8 +49,8 @@ def main(ckpt_dir: str, batch_size: int = 128) -> float:
             feats, non_id_type_features=[d], labels=[lab], requires_grad=False
         )
         tb = handler.preprocess(batch.to_bytes())  # the serving wire path
-        preds.append(handler.inference(tb).numpy())
-        lbls.append(tb.label_tensors[0].numpy())
+        preds.append(handler.inference(tb).cpu().numpy())
+        lbls.append(tb.label_tensors[0].cpu().numpy())
     infer_auc = auc_score(
         np.concatenate(lbls).ravel(), np.concatenate(preds).ravel()
     )

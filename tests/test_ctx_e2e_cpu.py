@@ -105,7 +105,9 @@ def test_training_learns_and_is_deterministic():
 def test_eval_ctx_shares_engine():
     losses, model = _train_once(n_batches=10)
     model.eval()
-    with eval_ctx(model=model) as ctx:
+    # same device as the TrainCtx whose engine it shares (a bare eval_ctx
+    # would pick cuda:0 on a GPU machine and move the model off the engine)
+    with eval_ctx(model=model, device_id=-1) as ctx:
         for tb in DataLoader(SynthDataset(n_batches=2, requires_grad=False)):
             pred, labels = ctx.forward(tb)
             assert pred.shape[0] == 32

@@ -120,8 +120,9 @@ def test_adult_income_gpu_deterministic():
 GPU_TRAIN_AUC = "0.8791397180312086"  # captured 2026-09-14 on MI355X
 
 
-def test_bench_default_config_one_step():
-    """bench.py's engine wiring at the flagship shape (tiny step count)."""
+def test_bench_default_config_one_step(tmp_path):
+    """bench.py's engine wiring at the flagship shape (tiny step count); the
+    graphed path also dumps its last step's outputs."""
     import subprocess
     import sys
     import json
@@ -129,7 +130,8 @@ def test_bench_default_config_one_step():
 
     out = subprocess.run(
         [sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
-         "--batch-size", "1024", "--rows", "1e6"],
+         "--batch-size", "1024", "--rows", "1e6",
+         "--dump-outputs", str(tmp_path)],
         capture_output=True, text=True, timeout=600,
         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
     )
@@ -138,6 +140,18 @@ def test_bench_default_config_one_step():
     res = json.loads(line)
     assert res["value"] > 0
     assert res["n_gpus"] == 1
+    assert res["steps"] == 3 and res["ms_per_step"] > 0
+    names = set(os.listdir(tmp_path))
+    assert names == {"loss.npy", "logits.npy", "dense_params.npy",
+                     "emb_sum.npy", "emb_sum_grad.npy"}, names
+    total = 0
+    for n in names:
+        a = np.load(os.path.join(tmp_path, n))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    assert np.load(os.path.join(tmp_path, "logits.npy")).size == 1024
+    assert np.abs(np.load(os.path.join(tmp_path, "emb_sum_grad.npy"))).max() > 0
 
 
 def test_flat_grad_views_accumulate_inside_graph():

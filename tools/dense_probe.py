@@ -1,5 +1,6 @@
 import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from persia_amd.ops import native
 C = native()
 dev = torch.device("cuda", 0)

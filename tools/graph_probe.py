@@ -3,7 +3,8 @@ import sys
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from persia_amd.models import DLRM
 
 torch.cuda.set_device(0)

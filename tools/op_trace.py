@@ -4,7 +4,8 @@ under torch.profiler and print op-level CUDA time grouped by input shape."""
 import runpy
 import sys
 
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from torch.profiler import ProfilerActivity, profile
 
@@ -13,7 +14,7 @@ sys.argv = ["bench.py", "--preset", "criteo", "--steps", "10",
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA],
              record_shapes=True) as prof:
     try:
-        runpy.run_path("/root/repo/bench.py", run_name="__main__")
+        runpy.run_path(os.path.join(sys.path[0], "bench.py"), run_name="__main__")
     except SystemExit:
         pass
 print(prof.key_averages(group_by_input_shape=True).table(

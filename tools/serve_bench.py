@@ -11,7 +11,8 @@ Run: python tools/serve_bench.py [batch_size ...]
 import sys
 import time
 
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 

@@ -11,7 +11,8 @@ so the digest groups by (kernel, grid).
 import sys
 import time
 
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from persia_amd.ops import native

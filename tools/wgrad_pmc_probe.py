@@ -1,7 +1,8 @@
 """Timing/PMC probe: the big-layer wgrad shape, kernel launched in a loop so
 counter runs attribute cleanly to wgrad_kernel."""
 import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from persia_amd.ops import native
 C = native()
 dev = torch.device("cuda", 0)

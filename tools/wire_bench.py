@@ -14,7 +14,8 @@ Run: python tools/wire_bench.py  (CPU-only safe; GPU part auto-skips)
 import sys
 import time
 
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from persia_amd.embedding.data import (
