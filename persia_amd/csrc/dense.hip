@@ -40,6 +40,94 @@ __device__ __forceinline__ short f2bf(float f) {
 }
 
 // ---------------------------------------------------------------------------
+// dReLU + bias-grad epilogue of the dgrad GEMMs (the DRELU variants below).
+// The GEMM computes the gradient w.r.t. a ReLU layer's OUTPUT; `mask` is that
+// output ([M,N] bf16, same shape as C).  Per element:
+//   v = mask > 0 ? acc : 0;  C = f2bf(v);  db[col] += bf2f(f2bf(v))
+// i.e. exactly what the plain dgrad store followed by relu_bwd_bias_kernel
+// produces, without the extra read-modify-write pass over C.  The "+ 0.0f"
+// mirrors the plain epilogue's "+ bval" with a null bias (it turns an
+// accumulator of -0 into +0 before rounding), so the stored bits match.
+// Column sums: 16 values per lane in registers -> the four lane>>4 groups by
+// cross-lane xor -> the two wr waves through LDS (`part`, [2][TBN] floats
+// carved from the idle staging image) -> ONE atomicAdd per column per block,
+// issued by consecutive threads as a contiguous run.  Rows >= M (the glds
+// kernel's clamped duplicates) and columns >= n_bias are excluded from the
+// mask read, the store and the sum.  Must be reached by all 256 threads.
+// The mask loads of FG accumulator fragments (4 per lane each) are issued
+// together and branch-free (addresses clamped into the tensor) ahead of the
+// dependent stores, so a round costs one memory latency.  FG covers all
+// 4 * NFRAG fragments (one round) where the kernel's occupancy leaves the
+// registers for it, fewer where it does not.
+template <int TBN, int NFRAG, int FG>
+__device__ __forceinline__ void drelu_bias_epilogue(
+    const f32x4 (&acc)[4][NFRAG], short* __restrict__ C,
+    const short* __restrict__ mask, float* __restrict__ db, float* part,
+    int M, int N, int n_bias, int m0, int n0, int wr, int wc, int lane,
+    int tid) {
+  constexpr int WN = TBN / 2;
+  const int fi = lane & 15;
+  // tile-local coordinates: element (rl, cl) sits 2 * (rl * N + cl) bytes
+  // past the block-uniform tile origin, which fits 32 bits (rl < 128, the
+  // binding bounds N) — one scalar base + a 32-bit lane offset per access
+  const int rl0 = wr * 64 + (lane >> 4) * 4;
+  const int cl0 = wc * WN + fi;
+  const int rl_max = M - 1 - m0, cl_max = N - 1 - n0;
+  const int64_t origin = ((int64_t)m0 * N + n0) * 2;
+  const char* mtile = (const char*)mask + origin;
+  char* ctile = (char*)C + origin;
+  float csum[NFRAG] = {};
+#pragma unroll
+  for (int f0 = 0; f0 < 4 * NFRAG; f0 += FG) {
+    short mk[FG][4];
+#pragma unroll
+    for (int f = 0; f < FG; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int am = (f0 + f) / NFRAG, bn = (f0 + f) % NFRAG;
+        const int rl = min(rl0 + am * 16 + r, rl_max);
+        const int cl = min(cl0 + bn * 16, cl_max);
+        mk[f][r] = *(const short*)(mtile + (unsigned)(rl * N + cl) * 2u);
+      }
+    // values and sums branch-free (selects), THEN the guarded stores: a
+    // store inside the same conditional as a use of a loaded value makes
+    // the compiler wait for each store before the next
+    short sv[FG][4];
+#pragma unroll
+    for (int f = 0; f < FG; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int am = (f0 + f) / NFRAG, bn = (f0 + f) % NFRAG;
+        const bool ok = rl0 + am * 16 + r <= rl_max && cl0 + bn * 16 <= cl_max;
+        float v = acc[am][bn][r] + 0.0f;
+        v = bf2f(mk[f][r]) > 0.0f ? v : 0.0f;
+        sv[f][r] = f2bf(v);
+        csum[bn] += ok ? bf2f(sv[f][r]) : 0.0f;
+      }
+#pragma unroll
+    for (int f = 0; f < FG; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int am = (f0 + f) / NFRAG, bn = (f0 + f) % NFRAG;
+        const int rl = rl0 + am * 16 + r;
+        const int cl = cl0 + bn * 16;
+        if (rl <= rl_max && cl <= cl_max)
+          *(short*)(ctile + (unsigned)(rl * N + cl) * 2u) = sv[f][r];
+      }
+  }
+#pragma unroll
+  for (int bn = 0; bn < NFRAG; ++bn) {
+    float s = csum[bn];
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (lane < 16) part[wr * TBN + wc * WN + bn * 16 + fi] = s;
+  }
+  __syncthreads();
+  if (tid < TBN && n0 + tid < n_bias)
+    atomicAdd(&db[n0 + tid], part[tid] + part[TBN + tid]);
+}
+
+// ---------------------------------------------------------------------------
 // NT GEMM: C[M,N] = act(A[M,K] @ B[N,K]^T + bias[N]); A,B bf16 row-major.
 // mfma_f32_16x16x32_bf16 fragment maps (verified numerically on gfx950):
 //   A frag: lane holds A[i = lane&15][k = (lane>>4)*8 + j]
@@ -55,11 +143,15 @@ __device__ __forceinline__ short f2bf(float f) {
 // T14 async-STAGE split (guide §6 G15): the next tile's global loads are
 // issued into REGISTERS before the MFMA block (HBM latency hides under the
 // compute), LDS writes happen after it.
-template <int ACT, bool STORE_F32, bool TRANS_B, int TBN, int TBK>
+// DRELU: dgrad variant with the dReLU + bias-grad epilogue above (ACT = 0,
+// bf16 store, no bias); mask/db/n_bias are unused otherwise.
+template <int ACT, bool STORE_F32, bool TRANS_B, int TBN, int TBK,
+          bool DRELU = false>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     const float* __restrict__ bias, void* __restrict__ C, int M, int N,
-    int K) {
+    int K, const short* __restrict__ mask, float* __restrict__ db,
+    int n_bias) {
   constexpr int LK = TBK + PAD;
   __shared__ short lds_a[2][BM * LK];
   __shared__ short lds_b[2][TBN * LK];
@@ -169,6 +261,13 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
     __syncthreads();
   }
 
+  if constexpr (DRELU) {
+    // the loop's trailing barrier retired every read of lds_a
+    drelu_bias_epilogue<TBN, NFRAG, (TBK == 64 ? 4 * NFRAG : 1)>(
+        acc, (short*)C, mask, db, (float*)&lds_a[0][0], M, N, n_bias, m0, n0,
+        wr, wc, lane, tid);
+    return;
+  }
 #pragma unroll
   for (int am = 0; am < 4; ++am) {
 #pragma unroll
@@ -328,11 +427,13 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(
 // conflict-spreading XOR applied to the SOURCE addresses and the fragment
 // reads (the same involution on both sides — rule 21).
 // Constraints: K % 64 == 0, N % 128 == 0 (launcher falls back otherwise).
-template <int ACT, bool STORE_F32, int TBN>
+// DRELU: as in gemm_nt_kernel (dgrad with the dReLU + bias-grad epilogue).
+template <int ACT, bool STORE_F32, int TBN, bool DRELU = false>
 __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     const float* __restrict__ bias, void* __restrict__ C, int M, int N,
-    int K) {
+    int K, const short* __restrict__ mask, float* __restrict__ db,
+    int n_bias) {
   constexpr int TBK = 64;  // 128 B per image row
   constexpr int WN = TBN / 2;      // per-wave N extent (2x2 wave grid)
   constexpr int NFRAG = WN / 16;
@@ -406,6 +507,13 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
     buf ^= 1;
   }
 
+  if constexpr (DRELU) {
+    // the loop's trailing wait + barrier retired every access to lds_a
+    drelu_bias_epilogue<TBN, NFRAG, 4 * NFRAG>(acc, (short*)C, mask, db,
+                                       (float*)&lds_a[0][0], M, N, n_bias,
+                                       m0, n0, wr, wc, lane, tid);
+    return;
+  }
 #pragma unroll
   for (int am = 0; am < 4; ++am) {
 #pragma unroll
@@ -805,26 +913,14 @@ static hipStream_t dcur_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
-// C = act(A @ op(B) + bias); A [M,K] bf16.
-// trans_b == 0: B is [N, K] (torch weight layout), C = A @ B^T.
-// trans_b == 1: B is [K, N] row-major, C = A @ B (the dgrad case: pass the
-//               [N_layer, K_layer] weight directly as the [K,N] operand).
-torch::Tensor gemm_nt_bias_act(torch::Tensor A, torch::Tensor B,
-                               torch::Tensor bias, int64_t act,
-                               int64_t out_f32, int64_t trans_b) {
-  TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
-              B.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(A.is_contiguous() && B.is_contiguous());
-  const int M = (int)A.size(0), K = (int)A.size(1);
-  const int N = (int)(trans_b ? B.size(1) : B.size(0));
-  TORCH_CHECK((trans_b ? B.size(0) : B.size(1)) == K, "gemm_nt shape mismatch");
-  TORCH_CHECK(K % BK == 0, "K must be a multiple of 32 (pad)");
-  TORCH_CHECK(N % 8 == 0, "N must be a multiple of 8");
-  auto C = torch::empty(
-      {M, N},
-      torch::TensorOptions()
-          .dtype(out_f32 ? torch::kFloat32 : torch::kBFloat16)
-          .device(A.device()));
+// Shape dispatch shared by gemm_nt_bias_act and dgrad_drelu_bias: both pick
+// the same kernel family and tile config for the same (M, N, K, trans_b).
+enum GemmFamily { kGemmV1 = 0, kGemmGlds = 1, kGemmGlds3 = 2 };
+struct GemmPlan {
+  int family, tbn, tbk, grid;
+};
+
+static GemmPlan gemm_plan(int M, int N, int K, bool trans_b) {
   const int m_tiles = (M + BM - 1) / BM;
   // v2 glds pipeline when shapes allow (PA_GEMM_V2=0 reverts)
   static const bool v2_on = [] {
@@ -845,38 +941,10 @@ torch::Tensor gemm_nt_bias_act(torch::Tensor A, torch::Tensor B,
     const char* e = getenv("PA_GEMM_V3");
     return e && atoi(e) != 0;
   }();
-  if (v3_on && v2_128) {
-    const int grid = m_tiles * (N / 128);
-    const float* bias_p = bias.numel() ? bias.data_ptr<float>() : nullptr;
-#define PA_GEMM3(ACTV, F32V)                                                  \
-  hipLaunchKernelGGL((gemm_nt_glds3_kernel<ACTV, F32V>), dim3(grid),          \
-                     dim3(256), 0, dcur_stream(),                             \
-                     (const bf16*)A.data_ptr(), (const bf16*)B.data_ptr(),    \
-                     bias_p, C.data_ptr(), M, N, K)
-    if (act == 1) { if (out_f32) PA_GEMM3(1, true); else PA_GEMM3(1, false); }
-    else          { if (out_f32) PA_GEMM3(0, true); else PA_GEMM3(0, false); }
-#undef PA_GEMM3
-    return C;
-  }
+  if (v3_on && v2_128) return {kGemmGlds3, 128, 64, m_tiles * (N / 128)};
   if (v2_128 || v2_64) {
     const int tbn = v2_128 ? 128 : 64;
-    const int grid = m_tiles * (N / tbn);
-    const float* bias_p = bias.numel() ? bias.data_ptr<float>() : nullptr;
-#define PA_GEMM2(ACTV, F32V, TBNV)                                            \
-  hipLaunchKernelGGL((gemm_nt_glds_kernel<ACTV, F32V, TBNV>), dim3(grid),     \
-                     dim3(256), 0, dcur_stream(),                             \
-                     (const bf16*)A.data_ptr(), (const bf16*)B.data_ptr(),    \
-                     bias_p, C.data_ptr(), M, N, K)
-#define PA_GEMM2_T(ACTV, F32V)                                                \
-  do {                                                                        \
-    if (v2_128) PA_GEMM2(ACTV, F32V, 128);                                    \
-    else PA_GEMM2(ACTV, F32V, 64);                                            \
-  } while (0)
-    if (act == 1) { if (out_f32) PA_GEMM2_T(1, true); else PA_GEMM2_T(1, false); }
-    else          { if (out_f32) PA_GEMM2_T(0, true); else PA_GEMM2_T(0, false); }
-#undef PA_GEMM2_T
-#undef PA_GEMM2
-    return C;
+    return {kGemmGlds, tbn, 64, m_tiles * (N / tbn)};
   }
   // tile config: BK=64 halves barriers (needs K%64); BN=64 doubles the grid
   // (skinny layers underfill 256 CUs at BN=128); (128,64) exceeds 64KB LDS.
@@ -884,31 +952,131 @@ torch::Tensor gemm_nt_bias_act(torch::Tensor A, torch::Tensor B,
   const bool narrow =
       ((int64_t)m_tiles * ((N + 127) / 128) < 192 && N % 64 == 0) || k64;
   const int tbn = narrow ? 64 : 128;
-  const int grid = m_tiles * ((N + tbn - 1) / tbn);
-  const float* bias_ptr = bias.numel() ? bias.data_ptr<float>() : nullptr;
+  return {kGemmV1, tbn, k64 ? 64 : 32, m_tiles * ((N + tbn - 1) / tbn)};
+}
+
+// Launch the planned kernel.  DRELU selects the dgrad epilogue variant
+// (ACT = 0, bf16 out; the opt-in glds3 ring has no such variant and maps to
+// the 2-buffer glds kernel with the same 128-wide tile).
+template <int ACT, bool F32, bool DRELU>
+static void gemm_launch(const GemmPlan& p, bool trans_b, const void* A,
+                        const void* B, const float* bias, void* C, int M,
+                        int N, int K, const short* mask, float* db,
+                        int n_bias) {
   hipStream_t st = dcur_stream();
-#define PA_GEMM(ACTV, F32V, TBV, TBNV, TBKV)                                  \
-  hipLaunchKernelGGL((gemm_nt_kernel<ACTV, F32V, TBV, TBNV, TBKV>),           \
-                     dim3(grid), dim3(256), 0, st, (const bf16*)A.data_ptr(), \
-                     (const bf16*)B.data_ptr(), bias_ptr, C.data_ptr(), M, N, \
-                     K)
-#define PA_GEMM_CFG(ACTV, F32V, TBV)                                          \
+#define PA_GEMM_ARGS                                                          \
+  dim3(p.grid), dim3(256), 0, st, (const bf16*)A, (const bf16*)B, bias, C, M, \
+      N, K, mask, db, n_bias
+  if constexpr (!DRELU) {
+    if (p.family == kGemmGlds3) {
+      hipLaunchKernelGGL((gemm_nt_glds3_kernel<ACT, F32>), dim3(p.grid),
+                         dim3(256), 0, st, (const bf16*)A, (const bf16*)B,
+                         bias, C, M, N, K);
+      return;
+    }
+  }
+  if (p.family != kGemmV1) {
+    if (p.tbn == 128)
+      hipLaunchKernelGGL((gemm_nt_glds_kernel<ACT, F32, 128, DRELU>),
+                         PA_GEMM_ARGS);
+    else
+      hipLaunchKernelGGL((gemm_nt_glds_kernel<ACT, F32, 64, DRELU>),
+                         PA_GEMM_ARGS);
+    return;
+  }
+#define PA_GEMM_CFG(TBV)                                                      \
   do {                                                                        \
-    if (k64) PA_GEMM(ACTV, F32V, TBV, 64, 64);                                \
-    else if (narrow) PA_GEMM(ACTV, F32V, TBV, 64, 32);                        \
-    else PA_GEMM(ACTV, F32V, TBV, 128, 32);                                   \
+    if (p.tbk == 64)                                                          \
+      hipLaunchKernelGGL((gemm_nt_kernel<ACT, F32, TBV, 64, 64, DRELU>),      \
+                         PA_GEMM_ARGS);                                       \
+    else if (p.tbn == 64)                                                     \
+      hipLaunchKernelGGL((gemm_nt_kernel<ACT, F32, TBV, 64, 32, DRELU>),      \
+                         PA_GEMM_ARGS);                                       \
+    else                                                                      \
+      hipLaunchKernelGGL((gemm_nt_kernel<ACT, F32, TBV, 128, 32, DRELU>),     \
+                         PA_GEMM_ARGS);                                       \
   } while (0)
-#define PA_GEMM_T(ACTV, F32V)                                                 \
-  do {                                                                        \
-    if (trans_b) PA_GEMM_CFG(ACTV, F32V, true);                               \
-    else PA_GEMM_CFG(ACTV, F32V, false);                                      \
-  } while (0)
-  if (act == 1) { if (out_f32) PA_GEMM_T(1, true); else PA_GEMM_T(1, false); }
-  else          { if (out_f32) PA_GEMM_T(0, true); else PA_GEMM_T(0, false); }
-#undef PA_GEMM_T
+  if (trans_b) PA_GEMM_CFG(true);
+  else PA_GEMM_CFG(false);
 #undef PA_GEMM_CFG
-#undef PA_GEMM
+#undef PA_GEMM_ARGS
+}
+
+static void gemm_check_operands(const torch::Tensor& A, const torch::Tensor& B,
+                                int64_t trans_b, int& M, int& N, int& K) {
+  TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
+              B.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(A.is_contiguous() && B.is_contiguous());
+  M = (int)A.size(0);
+  K = (int)A.size(1);
+  N = (int)(trans_b ? B.size(1) : B.size(0));
+  TORCH_CHECK((trans_b ? B.size(0) : B.size(1)) == K, "gemm_nt shape mismatch");
+  TORCH_CHECK(K % BK == 0, "K must be a multiple of 32 (pad)");
+  TORCH_CHECK(N % 8 == 0, "N must be a multiple of 8");
+}
+
+// C = act(A @ op(B) + bias); A [M,K] bf16.
+// trans_b == 0: B is [N, K] (torch weight layout), C = A @ B^T.
+// trans_b == 1: B is [K, N] row-major, C = A @ B (the dgrad case: pass the
+//               [N_layer, K_layer] weight directly as the [K,N] operand).
+torch::Tensor gemm_nt_bias_act(torch::Tensor A, torch::Tensor B,
+                               torch::Tensor bias, int64_t act,
+                               int64_t out_f32, int64_t trans_b) {
+  int M, N, K;
+  gemm_check_operands(A, B, trans_b, M, N, K);
+  auto C = torch::empty(
+      {M, N},
+      torch::TensorOptions()
+          .dtype(out_f32 ? torch::kFloat32 : torch::kBFloat16)
+          .device(A.device()));
+  const GemmPlan p = gemm_plan(M, N, K, trans_b != 0);
+  const float* bias_p = bias.numel() ? bias.data_ptr<float>() : nullptr;
+#define PA_GEMM_GO(ACTV, F32V)                                                \
+  gemm_launch<ACTV, F32V, false>(p, trans_b != 0, A.data_ptr(), B.data_ptr(), \
+                                 bias_p, C.data_ptr(), M, N, K, nullptr,      \
+                                 nullptr, 0)
+  if (act == 1) { if (out_f32) PA_GEMM_GO(1, true); else PA_GEMM_GO(1, false); }
+  else          { if (out_f32) PA_GEMM_GO(0, true); else PA_GEMM_GO(0, false); }
+#undef PA_GEMM_GO
   return C;
+}
+
+// dgrad through a ReLU producer in one kernel: dx = (g @ op(W)) masked by
+// `mask` (the producer's saved bf16 output, [M, N] like dx), with the masked
+// gradient's column sums ACCUMULATED into db[0:n_bias] (f32; a pre-zeroed
+// side-band slot or torch.zeros).  Bit-identical dx to gemm_nt_bias_act(g, W,
+// empty, 0, 0, trans_b) followed by relu_bwd; same kernel config per shape.
+torch::Tensor dgrad_drelu_bias(torch::Tensor g, torch::Tensor W,
+                               int64_t trans_b, torch::Tensor mask,
+                               torch::Tensor db, int64_t n_bias) {
+  int M, N, K;
+  gemm_check_operands(g, W, trans_b, M, N, K);
+  TORCH_CHECK(mask.scalar_type() == torch::kBFloat16 && mask.is_contiguous() &&
+                  mask.dim() == 2 && mask.size(0) == M && mask.size(1) == N,
+              "dgrad_drelu_bias: mask must be contiguous bf16 [M, N]");
+  TORCH_CHECK(db.scalar_type() == torch::kFloat32 && db.is_contiguous());
+  TORCH_CHECK(n_bias >= 0 && n_bias <= N && db.numel() >= n_bias,
+              "dgrad_drelu_bias: n_bias out of range");
+  TORCH_CHECK(N <= (1 << 23), "dgrad_drelu_bias: N too large");  // 32-bit tile offsets
+  TORCH_CHECK(mask.device() == g.device() && db.device() == g.device());
+  auto dx = torch::empty(
+      {M, N}, torch::TensorOptions().dtype(torch::kBFloat16).device(g.device()));
+  const GemmPlan p = gemm_plan(M, N, K, trans_b != 0);
+  gemm_launch<0, false, true>(p, trans_b != 0, g.data_ptr(), W.data_ptr(),
+                              nullptr, dx.data_ptr(), M, N, K,
+                              (const short*)mask.data_ptr(),
+                              db.data_ptr<float>(), (int)n_bias);
+  return dx;
+}
+
+// Which kernel the dispatch above picks for a shape, e.g. "v1:64x32",
+// "glds:128" (tests assert their shapes reach the intended branch).
+std::string gemm_nt_config(int64_t M, int64_t N, int64_t K, int64_t trans_b) {
+  const GemmPlan p = gemm_plan((int)M, (int)N, (int)K, trans_b != 0);
+  if (p.family == kGemmV1)
+    return "v1:" + std::to_string(p.tbn) + "x" + std::to_string(p.tbk);
+  return std::string(p.family == kGemmGlds3 ? "glds3:" : "glds:") +
+         std::to_string(p.tbn);
 }
 
 // -> g_eff; db accumulated into the given f32 buffer (pre-zeroed slot or
@@ -1074,6 +1242,10 @@ torch::Tensor bce_bwd(torch::Tensor sig, torch::Tensor y, torch::Tensor g) {
 void init_dense(pybind11::module_& m) {
   m.def("gemm_nt_bias_act", &gemm_nt_bias_act,
         "bf16 MFMA GEMM (A @ B^T) with fused bias+activation");
+  m.def("dgrad_drelu_bias", &dgrad_drelu_bias,
+        "dgrad GEMM with fused ReLU-backward mask + bias-grad column sums");
+  m.def("gemm_nt_config", &gemm_nt_config,
+        "kernel family / tile config the GEMM dispatch picks for a shape");
   m.def("relu_bwd", &relu_bwd, "g * (out > 0)");
   m.def("relu_bwd_bias", &relu_bwd_bias,
         "relu backward fused with the bias column-sum accumulation");
