@@ -21,7 +21,7 @@ Two implementations with identical semantics:
   also the CPU execution backend).
 * :class:`HipEmbeddingStore` — HBM-resident, HIP kernels via persia_amd._C.
 """
-from typing import Optional, Tuple
+from typing import Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -229,6 +229,29 @@ class EmbeddingStoreBase:
 
     def import_rows(self, signs: np.ndarray, inner: np.ndarray) -> None:
         raise NotImplementedError
+
+    def export_chunks(
+        self, chunk_rows: int
+    ) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
+        """Stream ``export_rows()`` as (signs, inner) pieces of at most
+        ``chunk_rows`` records, in the same order.  A piece is only valid
+        until the generator is advanced (backends may reuse staging
+        buffers); copy it to keep it.  This default slices one whole-table
+        export; the HIP backend streams in bounded memory."""
+        chunk_rows = max(1, int(chunk_rows))
+        signs, inner = self.export_rows()
+        for lo in range(0, len(signs), chunk_rows):
+            yield signs[lo:lo + chunk_rows], inner[lo:lo + chunk_rows]
+
+    def import_chunk(self, signs: np.ndarray, inner: np.ndarray) -> None:
+        """Insert one chunk of a streamed load (own tick per chunk)."""
+        self.import_rows(np.asarray(signs), np.asarray(inner))
+
+    def finish_import(self) -> int:
+        """End of a streamed load: number of rows offered to ``import_chunk``
+        since the last call that found no slot and were dropped (0 where the
+        backend does not count)."""
+        return 0
 
     def clear(self) -> None:
         raise NotImplementedError
@@ -490,6 +513,10 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         self._opt_code = {"sgd": 0, "adagrad": 1, "adam": 2}[optimizer.kind]
         self._probe_stream: Optional[torch.cuda.Stream] = None
         self._restore_tick: Optional[int] = None
+        self._ckpt_stream: Optional[torch.cuda.Stream] = None
+        # streamed-load accounting: rows offered (host) vs rows landed (device)
+        self._imported = torch.zeros(1, dtype=torch.int64, device=device)
+        self._import_offered = 0
         self.evicted_total = 0  # host-side eviction count (spill drains)
         self._no_evict = (
             torch.empty(0, dtype=torch.int64, device=device),
@@ -768,6 +795,126 @@ class HipEmbeddingStore(EmbeddingStoreBase):
             self.keys, self.ticks, self.arena, keys_t, rows_t, tick, *ev
         )
         self._drain_evictions(ev)
+
+    @property
+    def ckpt_stream(self) -> "torch.cuda.Stream":
+        """Dedicated stream of the streaming dump, so a non-blocking dump
+        does not queue behind (or in front of) the training stream's work."""
+        if self._ckpt_stream is None:
+            self._ckpt_stream = torch.cuda.Stream(device=self.device)
+        return self._ckpt_stream
+
+    def export_chunks(
+        self, chunk_rows: int
+    ) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
+        """Bounded-memory export in ``export_rows()`` order: slot windows of
+        ``chunk_rows`` slots are compacted on the device
+        (csrc/checkpoint.hip) into two staging buffers and copied, ``count``
+        rows each, into two pinned host buffers; the spill tier follows.
+        While the consumer handles window k, window k+1 is already compacted
+        and on its way to the host.  Yields views of the pinned buffers,
+        valid until the generator is advanced."""
+        chunk_rows = max(1, int(chunk_rows))
+        self.flush_spill()
+        cap = min(chunk_rows, self.n_slots)
+        n_win = (self.n_slots + cap - 1) // cap
+        st = self.ckpt_stream
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(st):
+            st.wait_event(ready)  # table state as of the caller's stream
+            dev = [
+                (
+                    torch.empty(cap, dtype=torch.int64, device=self.device),
+                    torch.empty(cap, self.row_width, dtype=torch.float32,
+                                device=self.device),
+                    torch.empty(1, dtype=torch.int32, device=self.device),
+                )
+                for _ in range(2)
+            ]
+        pin = [
+            (
+                torch.empty(cap, dtype=torch.int64, pin_memory=True),
+                torch.empty(cap, self.row_width, dtype=torch.float32,
+                            pin_memory=True),
+                torch.empty(1, dtype=torch.int32, pin_memory=True),
+            )
+            for _ in range(2)
+        ]
+        counted = [torch.cuda.Event() for _ in range(2)]
+        copied = [torch.cuda.Event() for _ in range(2)]
+
+        def stage(k: int) -> int:
+            """Queue window k (compaction, count readback, then the copy of
+            exactly ``count`` rows); returns its count."""
+            b = k % 2
+            d_signs, d_rows, d_count = dev[b]
+            p_signs, p_rows, p_count = pin[b]
+            with torch.cuda.stream(st):
+                self._C.store_export_window(
+                    self.keys, self.arena, k * cap,
+                    min(self.n_slots, (k + 1) * cap), d_signs, d_rows, d_count,
+                )
+                p_count.copy_(d_count, non_blocking=True)
+                counted[b].record(st)
+                counted[b].synchronize()
+                c = int(p_count.item())
+                if c:
+                    p_signs[:c].copy_(d_signs[:c], non_blocking=True)
+                    p_rows[:c].copy_(d_rows[:c], non_blocking=True)
+                copied[b].record(st)
+            return c
+
+        c = stage(0)
+        for k in range(n_win):
+            c_next = stage(k + 1) if k + 1 < n_win else 0
+            b = k % 2
+            copied[b].synchronize()
+            if c:
+                yield (
+                    pin[b][0][:c].numpy().view(np.uint64),
+                    pin[b][1][:c].numpy(),
+                )
+            c = c_next
+        sp = self.spill.export() if self.spill is not None and len(self.spill) else None
+        if sp is not None:
+            sp_keys, sp_rows = sp
+            for lo in range(0, len(sp_keys), chunk_rows):
+                yield (
+                    hashing.splitmix64_inv(sp_keys[lo:lo + chunk_rows]),
+                    sp_rows[lo:lo + chunk_rows],
+                )
+
+    def import_chunk(self, signs: np.ndarray, inner: np.ndarray) -> None:
+        """One chunk of a streamed load: staged through pinned memory; the
+        sign mixing, the slot claim, the eviction log and the row-width
+        adaptation all run in ``store_import_signs``."""
+        n = len(signs)
+        if n == 0:
+            return
+        assert inner.shape[0] == n and inner.shape[1] > 0
+        p_signs = torch.empty(n, dtype=torch.int64, pin_memory=True)
+        p_rows = torch.empty(n, inner.shape[1], dtype=torch.float32, pin_memory=True)
+        np.copyto(p_signs.numpy().view(np.uint64), signs, casting="same_kind")
+        np.copyto(p_rows.numpy(), inner, casting="same_kind")
+        signs_t = p_signs.to(self.device, non_blocking=True)
+        rows_t = p_rows.to(self.device, non_blocking=True)
+        tick = self.next_tick()
+        ev = self._evict_buffers(n)
+        self._C.store_import_signs(
+            self.keys, self.ticks, self.arena, signs_t, rows_t, tick,
+            float(self.optimizer.state_init(self.dim)), *ev, self._imported,
+        )
+        self._import_offered += n
+        self._drain_evictions(ev)
+
+    def finish_import(self) -> int:
+        if self._import_offered == 0:
+            return 0
+        dropped = self._import_offered - int(self._imported.item())
+        self._import_offered = 0
+        self._imported.zero_()
+        return dropped
 
     def clear(self) -> None:
         self.keys.zero_()

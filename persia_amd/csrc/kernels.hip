@@ -30,6 +30,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "probe.h"
 
 using ull = unsigned long long;
 
@@ -56,61 +57,6 @@ __device__ __forceinline__ long long probe_find(const ull* __restrict__ keys,
     }
   }
   return -1;
-}
-
-// Probe-or-claim with bounded-window LRU eviction (store.py _probe_or_claim).
-// Returns slot; *is_new = 1 when this thread claimed it (must init the row).
-// Rows touched at the CURRENT tick are never eviction victims, so concurrent
-// claims within one batch cannot evict each other; when the whole window is
-// current-tick the key overflows to a miss (bounded churn).
-__device__ long long probe_claim(ull* __restrict__ keys,
-                                 unsigned* __restrict__ ticks,
-                                 int64_t n_buckets, ull k, unsigned cur_tick,
-                                 int* is_new, ull* victim_out) {
-  const int64_t mask = n_buckets - 1;
-  const int64_t b = (int64_t)(k & (ull)mask);
-  for (int attempt = 0; attempt < 16; ++attempt) {
-    long long empty = -1;
-    long long victim = -1;
-    unsigned victim_tick = 0xFFFFFFFFu;
-    ull victim_key = 0;
-    for (int p = 0; p < PA_PROBE_BUCKETS; ++p) {
-      const int64_t base = ((b + p) & mask) * PA_BUCKET_SIZE;
-#pragma unroll
-      for (int s = 0; s < PA_BUCKET_SIZE; ++s) {
-        const int64_t i = base + s;
-        const ull ki = keys[i];
-        if (ki == k) { *is_new = 0; return i; }
-        if (ki == PA_EMPTY_KEY) {
-          if (empty < 0) empty = i;
-        } else {
-          const unsigned t = ticks[i];
-          if (t != cur_tick && (victim < 0 || t < victim_tick)) {
-            victim = i; victim_tick = t; victim_key = ki;
-          }
-        }
-      }
-    }
-    if (empty >= 0) {
-      if (atomicCAS((ull*)&keys[empty], PA_EMPTY_KEY, k) == PA_EMPTY_KEY) {
-        ticks[empty] = cur_tick;  // publish before peers pick victims
-        *is_new = 1; return empty;
-      }
-      continue;  // lost the race; rescan
-    }
-    if (victim >= 0) {
-      if (atomicCAS((ull*)&keys[victim], victim_key, k) == victim_key) {
-        ticks[victim] = cur_tick;
-        *is_new = 1;
-        if (victim_out) *victim_out = victim_key;
-        return victim;
-      }
-      continue;
-    }
-    break;  // every slot is current-tick: overflow
-  }
-  *is_new = 0;
-  return -1;  // give up: treated as a non-admitted miss
 }
 
 // Eviction log (host-DRAM spill tier): a claim that evicts appends the
@@ -1772,12 +1718,14 @@ torch::Tensor sign_prep_stack(torch::Tensor values, torch::Tensor in_starts,
 void init_dense(pybind11::module_& m);     // csrc/dense.hip
 void init_engine(pybind11::module_& m);    // csrc/engine.cpp
 void init_interact(pybind11::module_& m);  // csrc/interact.hip
+void init_checkpoint(pybind11::module_& m);  // csrc/checkpoint.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "persia_amd HIP kernels (gfx950)";
   init_dense(m);
   init_engine(m);
   init_interact(m);
+  init_checkpoint(m);
   m.def("store_lookup", &store_lookup, "hash-table lookup/insert + gather");
   m.def("store_probe", &store_probe, "probe-only (spill-tier miss detection)");
   m.def("store_lookup_sums", &store_lookup_sums,

@@ -19,6 +19,7 @@ ext = CUDAExtension(
         "persia_amd/csrc/kernels.hip",
         "persia_amd/csrc/dense.hip",
         "persia_amd/csrc/interact.hip",
+        "persia_amd/csrc/checkpoint.hip",
         "persia_amd/csrc/engine.cpp",
     ],
     include_dirs=[os.path.join(this_dir, "persia_amd", "csrc")],
