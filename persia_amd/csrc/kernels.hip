@@ -30,16 +30,38 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "optim.h"
 #include "probe.h"
 
 using ull = unsigned long long;
 
 namespace {
 
-__device__ __forceinline__ float pa_to_float(float x) { return x; }
-__device__ __forceinline__ float pa_to_float(__half x) { return __half2float(x); }
-__device__ __forceinline__ float pa_to_float(__hip_bfloat16 x) {
-  return __bfloat162float(x);
+// Column ownership of one lane.  Dims that divide the wave pack G = 64/dim
+// keys (or segments) per wave: lane -> key `sub`, the single column c0.
+// Every other dim gives the whole wave to one key: columns c0 = lane,
+// lane + 64, ...  `st` is both the column stride and the subgroup width.
+struct PaLanes {
+  int G, sub, c0, st;
+};
+__device__ __forceinline__ PaLanes pa_lanes(int lane, int dim) {
+  PaLanes l;
+  l.G = (dim < PA_WAVE && (PA_WAVE % dim) == 0) ? PA_WAVE / dim : 1;
+  l.sub = (l.G > 1) ? lane / dim : 0;
+  l.c0 = (l.G > 1) ? lane % dim : lane;
+  l.st = (l.G > 1) ? dim : PA_WAVE;
+  return l;
+}
+
+// Seeded init of a freshly claimed row: emb columns from the sign's seed
+// (bit-identical to core/store.py row_init), optimizer state to state_init.
+__device__ __forceinline__ void pa_init_row(float* row, ull key,
+                                            int dim, int row_width, double lo,
+                                            double hi, float state_init,
+                                            int c0, int st) {
+  const uint64_t seed = pa_init_seed(pa_splitmix64_inv((uint64_t)key));
+  for (int c = c0; c < dim; c += st) row[c] = pa_init_val(seed, c, lo, hi);
+  for (int c = dim + c0; c < row_width; c += st) row[c] = state_init;
 }
 
 // ---------------------------------------------------------------- store probe
@@ -141,35 +163,27 @@ __global__ void init_gather_kernel(float* __restrict__ arena,
   const int wave = threadIdx.x / PA_WAVE;
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
-  const int G = (dim < PA_WAVE && (PA_WAVE % dim) == 0) ? PA_WAVE / dim : 1;
-  const int sub = (G > 1) ? lane / dim : 0;
-  const int c0 = (G > 1) ? lane % dim : lane;
-  const int64_t n_waveitems = (n + G - 1) / G;
+  const PaLanes L = pa_lanes(lane, dim);
+  const int c0 = L.c0, st = L.st;
+  const int64_t n_waveitems = (n + L.G - 1) / L.G;
   for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
        w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t i = w * G + sub;
+    const int64_t i = w * L.G + L.sub;
     if (i >= n) continue;
     const long long slot = slots[i];
     OutT* dst = out + i * dim;
     if (slot < 0) {
-      for (int c = c0; c < dim; c += PA_WAVE) pa_store_out(0.0f, dst + c);
+      for (int c = c0; c < dim; c += st) pa_store_out(0.0f, dst + c);
       continue;
     }
     float* row = arena + (int64_t)slot * row_width;
-    const int st = (G > 1) ? dim : PA_WAVE;  // subgroup stride
     if (evict_rows && is_new[i] && evict_idx[i] >= 0) {
       // spill: save the victim's full row before overwriting it
       float* spill = evict_rows + evict_idx[i] * row_width;
       for (int c = c0; c < row_width; c += st) spill[c] = row[c];
     }
-    if (is_new[i]) {
-      const uint64_t sign = pa_splitmix64_inv((uint64_t)query[i]);
-      const uint64_t seed = pa_init_seed(sign);
-      for (int c = c0; c < dim; c += st)
-        row[c] = pa_init_val(seed, c, lo, hi);
-      for (int c = dim + c0; c < row_width; c += st)
-        row[c] = state_init;
-    }
+    if (is_new[i])
+      pa_init_row(row, query[i], dim, row_width, lo, hi, state_init, c0, st);
     for (int c = c0; c < dim; c += st) pa_store_out(row[c], dst + c);
   }
 }
@@ -193,14 +207,12 @@ __global__ void init_scatter_kernel(float* __restrict__ arena,
   const int wave = threadIdx.x / PA_WAVE;
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
-  const int G = (dim < PA_WAVE && (PA_WAVE % dim) == 0) ? PA_WAVE / dim : 1;
-  const int sub = (G > 1) ? lane / dim : 0;
-  const int c0 = (G > 1) ? lane % dim : lane;
-  const int st = (G > 1) ? dim : PA_WAVE;
-  const int64_t n_waveitems = (n + G - 1) / G;
+  const PaLanes L = pa_lanes(lane, dim);
+  const int c0 = L.c0, st = L.st;
+  const int64_t n_waveitems = (n + L.G - 1) / L.G;
   for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
        w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t i = w * G + sub;
+    const int64_t i = w * L.G + L.sub;
     if (i >= n) continue;
     const long long slot = slots[i];
     const int64_t lo_p = ustarts[i], hi_p = ustarts[i + 1];
@@ -212,14 +224,8 @@ __global__ void init_scatter_kernel(float* __restrict__ arena,
       continue;
     }
     float* row = arena + (int64_t)slot * row_width;
-    if (is_new[i]) {
-      const uint64_t sign = pa_splitmix64_inv((uint64_t)query[i]);
-      const uint64_t seed = pa_init_seed(sign);
-      for (int c = c0; c < dim; c += st)
-        row[c] = pa_init_val(seed, c, lo, hi);
-      for (int c = dim + c0; c < row_width; c += st)
-        row[c] = state_init;
-    }
+    if (is_new[i])
+      pa_init_row(row, query[i], dim, row_width, lo, hi, state_init, c0, st);
     for (int64_t p = lo_p; p < hi_p; ++p) {
       __half* dst = sums + perm[p] * dim;
       for (int c = c0; c < dim; c += st) dst[c] = __float2half(row[c]);
@@ -227,8 +233,8 @@ __global__ void init_scatter_kernel(float* __restrict__ arena,
   }
 }
 
-// Dual-key init/scatter for full-wave dims (see scatter_update2_kernel for
-// the rationale: the slots->arena->sums chain is latency-bound on random
+// Dual-key init/scatter for full-wave dims (see scatter_update_multi_kernel
+// for the rationale: the slots->arena->sums chain is latency-bound on random
 // row granules; two independent keys per wave double the in-flight loads).
 // The rare fresh-init path falls back to per-key sequential work.
 __global__ void init_scatter2_kernel(float* __restrict__ arena,
@@ -253,18 +259,12 @@ __global__ void init_scatter2_kernel(float* __restrict__ arena,
     const long long slotA = slots[iA];
     const long long slotB = okB0 ? slots[iB] : -1;
     // fresh rows: seeded init first (rare in steady state)
-    if (is_new[iA] && slotA >= 0) {
-      float* row = arena + (int64_t)slotA * row_width;
-      const uint64_t seed = pa_init_seed(pa_splitmix64_inv((uint64_t)query[iA]));
-      for (int c = lane; c < dim; c += PA_WAVE) row[c] = pa_init_val(seed, c, lo, hi);
-      for (int c = dim + lane; c < row_width; c += PA_WAVE) row[c] = state_init;
-    }
-    if (okB0 && is_new[iB] && slotB >= 0) {
-      float* row = arena + (int64_t)slotB * row_width;
-      const uint64_t seed = pa_init_seed(pa_splitmix64_inv((uint64_t)query[iB]));
-      for (int c = lane; c < dim; c += PA_WAVE) row[c] = pa_init_val(seed, c, lo, hi);
-      for (int c = dim + lane; c < row_width; c += PA_WAVE) row[c] = state_init;
-    }
+    if (is_new[iA] && slotA >= 0)
+      pa_init_row(arena + (int64_t)slotA * row_width, query[iA], dim,
+                  row_width, lo, hi, state_init, lane, PA_WAVE);
+    if (okB0 && is_new[iB] && slotB >= 0)
+      pa_init_row(arena + (int64_t)slotB * row_width, query[iB], dim,
+                  row_width, lo, hi, state_init, lane, PA_WAVE);
     const int64_t loA = ustarts[iA], hiA = ustarts[iA + 1];
     const int64_t loB = okB0 ? ustarts[iB] : 0;
     const int64_t hiB = okB0 ? ustarts[iB + 1] : 0;
@@ -298,7 +298,7 @@ __global__ void init_scatter2_kernel(float* __restrict__ arena,
 
 // one wave per key: probe (lane-parallel over the 32-slot window) + fused
 // row-wise optimizer + weight bound.
-// opt: 0 = SGD, 1 = Adagrad, 2 = Adam.   params: see store.py _opt_params.
+// opt / p0..p3: see PaOptArgs (optim.h).
 __global__ void update_kernel(ull* __restrict__ table_keys,
                               unsigned* __restrict__ ticks,
                               float* __restrict__ arena,
@@ -313,6 +313,8 @@ __global__ void update_kernel(ull* __restrict__ table_keys,
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
   const int64_t mask = n_buckets - 1;
+  const PaOptArgs oa =
+      pa_opt_args(opt, p0, p1, p2, p3, b1_power, b2_power, weight_bound);
   for (int64_t i = (int64_t)blockIdx.x * waves_per_block + wave; i < n;
        i += (int64_t)gridDim.x * waves_per_block) {
     const ull k = query[i];
@@ -343,45 +345,34 @@ __global__ void update_kernel(ull* __restrict__ table_keys,
       if (lane == 0) atomicAdd(&skipped[1], 1);
       continue;
     }
-    if (opt == 0) {  // SGD: w -= lr*(g + wd*w)         p0=lr p1=wd
-      for (int c = lane; c < dim; c += PA_WAVE) {
-        float w = row[c] - p0 * (g[c] + p1 * row[c]);
-        if (weight_bound > 0.0f) w = fminf(fmaxf(w, -weight_bound), weight_bound);
-        row[c] = w;
-      }
-    } else if (opt == 1) {  // Adagrad  p0=lr p1=g_square_momentum p2=eps p3=vectorwise
-      if (p3 > 0.5f) {
+    if (opt == 0) {  // SGD
+      for (int c = lane; c < dim; c += PA_WAVE)
+        row[c] = pa_sgd(oa, row[c], g[c]);
+    } else if (opt == 1) {  // Adagrad
+      if (pa_adagrad_shared(oa)) {
         // shared scalar accumulator at row[dim]
         const float acc = row[dim];
         float gsq = 0.0f;
         for (int c = lane; c < dim; c += PA_WAVE) {
-          float w = row[c] - p0 * g[c] * rsqrtf(acc + p2);
-          if (weight_bound > 0.0f) w = fminf(fmaxf(w, -weight_bound), weight_bound);
-          row[c] = w;
+          row[c] = pa_adagrad_w(oa, row[c], acc, g[c]);
           gsq += g[c] * g[c];
         }
 #pragma unroll
         for (int off = PA_WAVE / 2; off > 0; off >>= 1)
           gsq += __shfl_down(gsq, off);
-        if (lane == 0) row[dim] = acc * p1 + gsq / (float)dim;
+        if (lane == 0) row[dim] = pa_adagrad_shared_acc(oa, acc, gsq, dim);
       } else {
         for (int c = lane; c < dim; c += PA_WAVE) {
           const float acc = row[dim + c];
-          float w = row[c] - p0 * g[c] * rsqrtf(acc + p2);
-          if (weight_bound > 0.0f) w = fminf(fmaxf(w, -weight_bound), weight_bound);
-          row[c] = w;
-          row[dim + c] = acc * p1 + g[c] * g[c];
+          row[c] = pa_adagrad_w(oa, row[c], acc, g[c]);
+          row[dim + c] = pa_adagrad_acc(oa, acc, g[c]);
         }
       }
-    } else {  // Adam  p0=lr p1=beta1 p2=beta2 p3=eps
-      const float om1 = 1.0f - p1, om2 = 1.0f - p2;
-      const float c1 = 1.0f / (1.0f - b1_power), c2 = 1.0f / (1.0f - b2_power);
+    } else {  // Adam
       for (int c = lane; c < dim; c += PA_WAVE) {
-        const float m = p1 * row[dim + c] + om1 * g[c];
-        const float v = p2 * row[2 * dim + c] + om2 * g[c] * g[c];
-        float w = row[c] - p0 * (m * c1) / (p3 + sqrtf(v * c2));
-        if (weight_bound > 0.0f) w = fminf(fmaxf(w, -weight_bound), weight_bound);
-        row[c] = w;
+        const float m = pa_adam_m(oa, row[dim + c], g[c]);
+        const float v = pa_adam_v(oa, row[2 * dim + c], g[c]);
+        row[c] = pa_adam_w(oa, row[c], m, v);
         row[dim + c] = m;
         row[2 * dim + c] = v;
       }
@@ -614,18 +605,16 @@ __global__ void segment_sum_kernel(const RowT* __restrict__ rows,
   const int wave = threadIdx.x / PA_WAVE;
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
-  const int G = (dim < PA_WAVE && (PA_WAVE % dim) == 0) ? PA_WAVE / dim : 1;
-  const int sub = (G > 1) ? lane / dim : 0;
-  const int c0 = (G > 1) ? lane % dim : lane;
-  const int64_t n_waveitems = (n_seg + G - 1) / G;
+  const PaLanes L = pa_lanes(lane, dim);
+  const int64_t n_waveitems = (n_seg + L.G - 1) / L.G;
   for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
        w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t s = w * G + sub;
+    const int64_t s = w * L.G + L.sub;
     if (s >= n_seg) continue;
     const int64_t lo = seg_offsets[s], hi = seg_offsets[s + 1];
     const float scale = seg_scale ? seg_scale[s] : 1.0f;
     __half* dst = out + s * dim;
-    for (int c = c0; c < dim; c += PA_WAVE) {
+    for (int c = L.c0; c < dim; c += L.st) {
       float acc = 0.0f;
       for (int64_t k = lo; k < hi; ++k) {
         acc += pa_to_float(rows[inverse[k] * dim + c]);
@@ -659,17 +648,10 @@ __global__ void grad_scatter_kernel(const GradT* __restrict__ grads,
     const int64_t lo = ustarts[u], hi = ustarts[u + 1];
     float* dst = out + u * dim;
     for (int c = lane; c < dim; c += PA_WAVE) {
-      float acc = 0.0f;
-      for (int64_t p = lo; p < hi; ++p) {
-        const int64_t s = seg_id[perm[p]];
-        if (s >= 0) {
-          // scale 0 skips the slot entirely (NaN-slot mask: never multiply a
-          // NaN gradient, even by zero); null scale = 1
-          const float sc = seg_scale ? seg_scale[s] : 1.0f;
-          if (sc != 0.0f) acc += pa_to_float(grads[s * dim + c]) * sc;
-        }
-      }
-      if (ACCUMULATE) dst[c] += acc; else dst[c] = acc;
+      float acc[1] = {0.0f};
+      pa_reduce_positions<1>(acc, grads, perm, seg_id, seg_scale, lo, hi, dim, c,
+                          PA_WAVE);
+      if (ACCUMULATE) dst[c] += acc[0]; else dst[c] = acc[0];
     }
   }
 }
@@ -691,27 +673,19 @@ __global__ void grad_scatter_idx_kernel(
   const int wave = threadIdx.x / PA_WAVE;
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
-  const int G = (dim < PA_WAVE && (PA_WAVE % dim) == 0) ? PA_WAVE / dim : 1;
-  const int sub = (G > 1) ? lane / dim : 0;
-  const int c0 = (G > 1) ? lane % dim : lane;
-  const int st = (G > 1) ? dim : PA_WAVE;
-  const int64_t n_waveitems = (n_unique + G - 1) / G;
+  const PaLanes L = pa_lanes(lane, dim);
+  const int64_t n_waveitems = (n_unique + L.G - 1) / L.G;
   for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
        w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t u = w * G + sub;
+    const int64_t u = w * L.G + L.sub;
     if (u >= n_unique) continue;
     const int64_t lo = ustarts[u], hi = ustarts[u + 1];
     OutT* dst = out + out_idx[u] * dim;
-    for (int c = c0; c < dim; c += st) {
-      float acc = 0.0f;
-      for (int64_t p = lo; p < hi; ++p) {
-        const int64_t s = seg_id[perm[p]];
-        if (s >= 0) {
-          const float sc = seg_scale ? seg_scale[s] : 1.0f;
-          if (sc != 0.0f) acc += __half2float(grads[s * dim + c]) * sc;
-        }
-      }
-      pa_store_out(acc, dst + c);
+    for (int c = L.c0; c < dim; c += L.st) {
+      float acc[1] = {0.0f};
+      pa_reduce_positions<1>(acc, grads, perm, seg_id, seg_scale, lo, hi, dim, c,
+                          L.st);
+      pa_store_out(acc[0], dst + c);
     }
   }
 }
@@ -736,12 +710,12 @@ __global__ void scatter_update_kernel(
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
   const int64_t mask = n_buckets - 1;
+  const PaOptArgs oa =
+      pa_opt_args(opt, p0, p1, p2, p3, b1_power, b2_power, weight_bound);
   // small dims pack 64/dim keys per wave (sub-wave groups)
-  const int G = (dim < PA_WAVE && (PA_WAVE % dim) == 0) ? PA_WAVE / dim : 1;
-  const int sub = (G > 1) ? lane / dim : 0;
-  const int c0 = (G > 1) ? lane % dim : lane;
-  const int st = (G > 1) ? dim : PA_WAVE;
-  const int sg = (G > 1) ? dim : PA_WAVE;  // subgroup width
+  const PaLanes L = pa_lanes(lane, dim);
+  const int G = L.G, sub = L.sub, c0 = L.c0, st = L.st;
+  const int sg = L.st;  // subgroup width
   const ull sg_mask = (sg >= 64) ? ~0ull : ((1ull << sg) - 1ull);
   const int64_t n_waveitems = (n + G - 1) / G;
   constexpr int WINDOW = PA_PROBE_BUCKETS * PA_BUCKET_SIZE;
@@ -777,18 +751,9 @@ __global__ void scatter_update_kernel(
     float acc[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) acc[t] = 0.0f;
-    if (ok) {
-      const int64_t lo = ustarts[u], hi = ustarts[u + 1];
-      for (int64_t p = lo; p < hi; ++p) {
-        const int64_t s = seg_id[perm[p]];
-        if (s < 0) continue;
-        const float sc = seg_scale ? seg_scale[s] : 1.0f;
-        if (sc == 0.0f) continue;
-        const __half* g = grads + s * dim;
-        for (int t = 0, c = c0; c < dim; c += st, ++t)
-          acc[t] += __half2float(g[c]) * sc;
-      }
-    }
+    if (ok)
+      pa_reduce_positions<8>(acc, grads, perm, seg_id, seg_scale, ustarts[u],
+                          ustarts[u + 1], dim, c0, st);
     bool has_nan = false;
     if (ok)
       for (int t = 0, c = c0; c < dim; c += st, ++t) has_nan |= isnan(acc[t]);
@@ -805,45 +770,36 @@ __global__ void scatter_update_kernel(
     if (opt == 0) {  // SGD
       for (int t = 0, c = c0; c < dim; c += st, ++t) {
         const float w0 = __builtin_nontemporal_load(&row[c]);
-        float w2 = w0 - p0 * (acc[t] + p1 * w0);
-        if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-        __builtin_nontemporal_store(w2, &row[c]);
+        __builtin_nontemporal_store(pa_sgd(oa, w0, acc[t]), &row[c]);
       }
     } else if (opt == 1) {  // Adagrad
-      if (p3 > 0.5f) {
+      if (pa_adagrad_shared(oa)) {
         const float a0 = row[dim];
         float gsq = 0.0f;
         for (int t = 0, c = c0; c < dim; c += st, ++t) {
           const float w0 = __builtin_nontemporal_load(&row[c]);
-          float w2 = w0 - p0 * acc[t] * rsqrtf(a0 + p2);
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &row[c]);
+          __builtin_nontemporal_store(pa_adagrad_w(oa, w0, a0, acc[t]), &row[c]);
           gsq += acc[t] * acc[t];
         }
         for (int off = sg / 2; off > 0; off >>= 1)
           gsq += __shfl_down(gsq, off, sg);
-        if (c0 == 0) row[dim] = a0 * p1 + gsq / (float)dim;
+        if (c0 == 0) row[dim] = pa_adagrad_shared_acc(oa, a0, gsq, dim);
       } else {
         for (int t = 0, c = c0; c < dim; c += st, ++t) {
           const float a0 = __builtin_nontemporal_load(&row[dim + c]);
           const float w0 = __builtin_nontemporal_load(&row[c]);
-          float w2 = w0 - p0 * acc[t] * rsqrtf(a0 + p2);
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &row[c]);
-          __builtin_nontemporal_store(a0 * p1 + acc[t] * acc[t], &row[dim + c]);
+          __builtin_nontemporal_store(pa_adagrad_w(oa, w0, a0, acc[t]), &row[c]);
+          __builtin_nontemporal_store(pa_adagrad_acc(oa, a0, acc[t]), &row[dim + c]);
         }
       }
     } else {  // Adam
-      const float om1 = 1.0f - p1, om2 = 1.0f - p2;
-      const float c1 = 1.0f / (1.0f - b1_power), c2 = 1.0f / (1.0f - b2_power);
       for (int t = 0, c = c0; c < dim; c += st, ++t) {
-        const float m = p1 * __builtin_nontemporal_load(&row[dim + c]) + om1 * acc[t];
-        const float v =
-            p2 * __builtin_nontemporal_load(&row[2 * dim + c]) + om2 * acc[t] * acc[t];
+        const float m = pa_adam_m(
+            oa, __builtin_nontemporal_load(&row[dim + c]), acc[t]);
+        const float v = pa_adam_v(
+            oa, __builtin_nontemporal_load(&row[2 * dim + c]), acc[t]);
         const float w0 = __builtin_nontemporal_load(&row[c]);
-        float w2 = w0 - p0 * (m * c1) / (p3 + sqrtf(v * c2));
-        if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-        __builtin_nontemporal_store(w2, &row[c]);
+        __builtin_nontemporal_store(pa_adam_w(oa, w0, m, v), &row[c]);
         __builtin_nontemporal_store(m, &row[dim + c]);
         __builtin_nontemporal_store(v, &row[2 * dim + c]);
       }
@@ -851,208 +807,21 @@ __global__ void scatter_update_kernel(
   }
 }
 
-// Dual-key variant for full-wave dims (64 <= dim <= 256): one wave updates
-// TWO unique keys with interleaved loads — the single-key kernel is
-// latency-bound on its probe -> grads -> arena dependent chain (random 1-2 KB
-// row granules), so doubling the independent in-flight accesses per wave
-// buys memory-level parallelism the scheduler can't extract across
-// grid-stride iterations (ballots/shfl block software pipelining).
-__global__ void scatter_update2_kernel(
-    ull* __restrict__ table_keys, unsigned* __restrict__ ticks,
-    float* __restrict__ arena, const ull* __restrict__ uniq,
-    const __half* __restrict__ grads, const int64_t* __restrict__ perm,
-    const int64_t* __restrict__ ustarts, const int64_t* __restrict__ seg_id,
-    const float* __restrict__ seg_scale, int64_t n, int dim, int row_width,
-    int64_t n_buckets, int opt, float p0, float p1, float p2, float p3,
-    float b1_power, float b2_power, float weight_bound,
-    int* __restrict__ skipped, const long long* __restrict__ n_dev) {
-  if (n_dev) n = *n_dev;
-  const int wave = threadIdx.x / PA_WAVE;
-  const int lane = threadIdx.x % PA_WAVE;
-  const int waves_per_block = blockDim.x / PA_WAVE;
-  const int64_t mask = n_buckets - 1;
-  constexpr int WINDOW = PA_PROBE_BUCKETS * PA_BUCKET_SIZE;  // 32
-  const int half = lane >> 5;   // probe phase: lanes 0-31 key A, 32-63 key B
-  const int widx = lane & 31;
-  const int64_t n_waveitems = (n + 1) / 2;
-  for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
-       w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t u = w * 2 + half;
-    const ull k = (u < n) ? uniq[u] : 0;
-    const bool active = (u < n) && (k != PA_EMPTY_KEY);
-    long long slot = -1;
-    if (active) {
-      const int64_t b = (int64_t)(k & (ull)mask);
-      const int p = widx / PA_BUCKET_SIZE;
-      const int s = widx % PA_BUCKET_SIZE;
-      const int64_t j = ((b + p) & mask) * PA_BUCKET_SIZE + s;
-      if (table_keys[j] == k) slot = j;
-    }
-    const unsigned long long found = __ballot(slot >= 0);
-    const unsigned long long nonzero = __ballot(k != PA_EMPTY_KEY);
-    const unsigned fA = (unsigned)(found & 0xFFFFFFFFull);
-    const unsigned fB = (unsigned)(found >> 32);
-    // empty-key (a2a padding) entries skip silently, not as misses
-    bool okA = (w * 2 + 0) < n && (nonzero & 1ull);
-    bool okB = (w * 2 + 1) < n && (nonzero >> 32 & 1ull);
-    if (okA && fA == 0) { if (lane == 0) atomicAdd(&skipped[0], 1); okA = false; }
-    if (okB && fB == 0) { if (lane == 0) atomicAdd(&skipped[0], 1); okB = false; }
-    const long long slotA = okA ? __shfl(slot, __ffs(fA) - 1) : -1;
-    const long long slotB = okB ? __shfl(slot, 32 + __ffs(fB) - 1) : -1;
-    // gradient accumulation (whole wave per key, interleaved when both are
-    // single-position — the overwhelmingly common case)
-    float accA[4] = {}, accB[4] = {};
-    const int64_t loA = ustarts[w * 2], hiA = okA ? ustarts[w * 2 + 1] : loA;
-    const int64_t loB = okB ? ustarts[w * 2 + 1] : 0;
-    const int64_t hiB = okB ? ustarts[w * 2 + 2] : loB;
-    if (okA && okB && hiA - loA == 1 && hiB - loB == 1) {
-      const int64_t sA = seg_id[perm[loA]], sB = seg_id[perm[loB]];
-      const float scA = (sA >= 0) ? (seg_scale ? seg_scale[sA] : 1.0f) : 0.0f;
-      const float scB = (sB >= 0) ? (seg_scale ? seg_scale[sB] : 1.0f) : 0.0f;
-      const __half* gA = grads + (sA >= 0 ? sA : 0) * dim;
-      const __half* gB = grads + (sB >= 0 ? sB : 0) * dim;
-      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-        accA[t] = scA * __half2float(gA[c]);
-        accB[t] = scB * __half2float(gB[c]);
-      }
-    } else {
-      if (okA)
-        for (int64_t p = loA; p < hiA; ++p) {
-          const int64_t s = seg_id[perm[p]];
-          if (s < 0) continue;
-          const float sc = seg_scale ? seg_scale[s] : 1.0f;
-          if (sc == 0.0f) continue;
-          const __half* g = grads + s * dim;
-          for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t)
-            accA[t] += __half2float(g[c]) * sc;
-        }
-      if (okB)
-        for (int64_t p = loB; p < hiB; ++p) {
-          const int64_t s = seg_id[perm[p]];
-          if (s < 0) continue;
-          const float sc = seg_scale ? seg_scale[s] : 1.0f;
-          if (sc == 0.0f) continue;
-          const __half* g = grads + s * dim;
-          for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t)
-            accB[t] += __half2float(g[c]) * sc;
-        }
-    }
-    bool nanA = false, nanB = false;
-    for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-      nanA |= isnan(accA[t]);
-      nanB |= isnan(accB[t]);
-    }
-    if (okA && __ballot(nanA) != 0) {
-      if (lane == 0) atomicAdd(&skipped[1], 1);
-      okA = false;
-    }
-    if (okB && __ballot(nanB) != 0) {
-      if (lane == 0) atomicAdd(&skipped[1], 1);
-      okB = false;
-    }
-    if (!okA && !okB) continue;
-    float* rowA = okA ? arena + (int64_t)slotA * row_width : nullptr;
-    float* rowB = okB ? arena + (int64_t)slotB * row_width : nullptr;
-    if (opt == 0) {  // SGD
-      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-        const float wA = okA ? __builtin_nontemporal_load(&rowA[c]) : 0.0f;
-        const float wB = okB ? __builtin_nontemporal_load(&rowB[c]) : 0.0f;
-        if (okA) {
-          float w2 = wA - p0 * (accA[t] + p1 * wA);
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &rowA[c]);
-        }
-        if (okB) {
-          float w2 = wB - p0 * (accB[t] + p1 * wB);
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &rowB[c]);
-        }
-      }
-    } else if (opt == 1) {  // Adagrad
-      if (p3 > 0.5f) {  // vectorwise-shared accumulator
-        const float a0A = okA ? rowA[dim] : 0.0f;
-        const float a0B = okB ? rowB[dim] : 0.0f;
-        float gsqA = 0.0f, gsqB = 0.0f;
-        for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-          const float wA = okA ? __builtin_nontemporal_load(&rowA[c]) : 0.0f;
-          const float wB = okB ? __builtin_nontemporal_load(&rowB[c]) : 0.0f;
-          if (okA) {
-            float w2 = wA - p0 * accA[t] * rsqrtf(a0A + p2);
-            if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-            __builtin_nontemporal_store(w2, &rowA[c]);
-            gsqA += accA[t] * accA[t];
-          }
-          if (okB) {
-            float w2 = wB - p0 * accB[t] * rsqrtf(a0B + p2);
-            if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-            __builtin_nontemporal_store(w2, &rowB[c]);
-            gsqB += accB[t] * accB[t];
-          }
-        }
-#pragma unroll
-        for (int off = PA_WAVE / 2; off > 0; off >>= 1) {
-          gsqA += __shfl_down(gsqA, off);
-          gsqB += __shfl_down(gsqB, off);
-        }
-        if (lane == 0) {
-          if (okA) rowA[dim] = a0A * p1 + gsqA / (float)dim;
-          if (okB) rowB[dim] = a0B * p1 + gsqB / (float)dim;
-        }
-      } else {
-        for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-          const float aA = okA ? __builtin_nontemporal_load(&rowA[dim + c]) : 0.0f;
-          const float aB = okB ? __builtin_nontemporal_load(&rowB[dim + c]) : 0.0f;
-          const float wA = okA ? __builtin_nontemporal_load(&rowA[c]) : 0.0f;
-          const float wB = okB ? __builtin_nontemporal_load(&rowB[c]) : 0.0f;
-          if (okA) {
-            float w2 = wA - p0 * accA[t] * rsqrtf(aA + p2);
-            if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-            __builtin_nontemporal_store(w2, &rowA[c]);
-            __builtin_nontemporal_store(aA * p1 + accA[t] * accA[t], &rowA[dim + c]);
-          }
-          if (okB) {
-            float w2 = wB - p0 * accB[t] * rsqrtf(aB + p2);
-            if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-            __builtin_nontemporal_store(w2, &rowB[c]);
-            __builtin_nontemporal_store(aB * p1 + accB[t] * accB[t], &rowB[dim + c]);
-          }
-        }
-      }
-    } else {  // Adam
-      const float om1 = 1.0f - p1, om2 = 1.0f - p2;
-      const float c1 = 1.0f / (1.0f - b1_power), c2 = 1.0f / (1.0f - b2_power);
-      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-        if (okA) {
-          const float m = p1 * __builtin_nontemporal_load(&rowA[dim + c]) + om1 * accA[t];
-          const float v =
-              p2 * __builtin_nontemporal_load(&rowA[2 * dim + c]) + om2 * accA[t] * accA[t];
-          const float w0 = __builtin_nontemporal_load(&rowA[c]);
-          float w2 = w0 - p0 * (m * c1) / (p3 + sqrtf(v * c2));
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &rowA[c]);
-          __builtin_nontemporal_store(m, &rowA[dim + c]);
-          __builtin_nontemporal_store(v, &rowA[2 * dim + c]);
-        }
-        if (okB) {
-          const float m = p1 * __builtin_nontemporal_load(&rowB[dim + c]) + om1 * accB[t];
-          const float v =
-              p2 * __builtin_nontemporal_load(&rowB[2 * dim + c]) + om2 * accB[t] * accB[t];
-          const float w0 = __builtin_nontemporal_load(&rowB[c]);
-          float w2 = w0 - p0 * (m * c1) / (p3 + sqrtf(v * c2));
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &rowB[c]);
-          __builtin_nontemporal_store(m, &rowB[dim + c]);
-          __builtin_nontemporal_store(v, &rowB[2 * dim + c]);
-        }
-      }
-    }
-  }
-}
+// Multi-key variant for full-wave dims: one wave updates Q unique keys with
+// interleaved loads — the single-key kernel is latency-bound on its probe ->
+// grads -> arena dependent chain (random 1-2 KB row granules), so Q
+// independent in-flight chains per wave buy memory-level parallelism the
+// scheduler can't extract across grid-stride iterations (ballots/shfl block
+// software pipelining).  Q = 4 for dim <= 128, Q = 2 for dim <= 256: the
+// register-resident gradient is acc[Q][8/Q] either way.  Probe: 64/Q lanes
+// per key, each lane scans Q/2 of the 32 window slots; after it the whole
+// wave works on every key.  All per-key loops unroll over the constexpr Q so
+// the per-key arrays stay in registers.
+template <int T>
+using PaAccVec = float __attribute__((ext_vector_type(T)));
 
-// Quad-key variant for dim <= 128 (acc fits 2 cols/lane/key): 4 independent
-// probe->grads->arena chains per wave.  Probe: 16 lanes per key, each lane
-// scans 2 of the 32 window slots.
-__global__ void scatter_update4_kernel(
+template <int Q>
+__global__ void scatter_update_multi_kernel(
     ull* __restrict__ table_keys, unsigned* __restrict__ ticks,
     float* __restrict__ arena, const ull* __restrict__ uniq,
     const __half* __restrict__ grads, const int64_t* __restrict__ perm,
@@ -1061,25 +830,33 @@ __global__ void scatter_update4_kernel(
     int64_t n_buckets, int opt, float p0, float p1, float p2, float p3,
     float b1_power, float b2_power, float weight_bound,
     int* __restrict__ skipped, const long long* __restrict__ n_dev) {
+  static_assert(Q == 2 || Q == 4, "two or four keys per wave");
+  constexpr int WINDOW = PA_PROBE_BUCKETS * PA_BUCKET_SIZE;  // 32
+  constexpr int PL = PA_WAVE / Q;   // probe lanes per key
+  constexpr int WS = WINDOW / PL;   // window slots per probe lane
+  constexpr int T = 8 / Q;          // columns per lane per key
+  constexpr ull PL_MASK = (1ull << PL) - 1ull;
   if (n_dev) n = *n_dev;
   const int wave = threadIdx.x / PA_WAVE;
   const int lane = threadIdx.x % PA_WAVE;
   const int waves_per_block = blockDim.x / PA_WAVE;
   const int64_t mask = n_buckets - 1;
-  const int kq = lane >> 4;   // probe phase: 16 lanes per key
-  const int widx = lane & 15;
-  const int64_t n_waveitems = (n + 3) / 4;
+  const PaOptArgs oa =
+      pa_opt_args(opt, p0, p1, p2, p3, b1_power, b2_power, weight_bound);
+  const int kq = lane / PL;
+  const int widx = lane % PL;
+  const int64_t n_waveitems = (n + Q - 1) / Q;
   for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
        w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t u = w * 4 + kq;
+    const int64_t u = w * Q + kq;
     const ull k = (u < n) ? uniq[u] : 0;
     const bool active = (u < n) && (k != PA_EMPTY_KEY);
     long long slot = -1;
     if (active) {
       const int64_t b = (int64_t)(k & (ull)mask);
 #pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int wi = widx + half * 16;
+      for (int h = 0; h < WS; ++h) {
+        const int wi = widx + h * PL;
         const int p = wi / PA_BUCKET_SIZE;
         const int s = wi % PA_BUCKET_SIZE;
         const int64_t j = ((b + p) & mask) * PA_BUCKET_SIZE + s;
@@ -1088,63 +865,62 @@ __global__ void scatter_update4_kernel(
     }
     const unsigned long long found = __ballot(slot >= 0);
     const unsigned long long nonzero = __ballot(k != PA_EMPTY_KEY);
-    bool ok[4];
-    long long slotk[4];
-    float* rowk[4];
+    bool ok[Q];
+    float* rowk[Q];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const unsigned fq = (unsigned)((found >> (16 * q)) & 0xFFFFull);
+    for (int q = 0; q < Q; ++q) {
+      const unsigned fq = (unsigned)((found >> (PL * q)) & PL_MASK);
       // empty-key (a2a padding) entries skip silently, not as misses
-      ok[q] = (w * 4 + q) < n && (nonzero >> (16 * q) & 1ull);
+      ok[q] = (w * Q + q) < n && (nonzero >> (PL * q) & 1ull);
       if (ok[q] && fq == 0) {
         if (lane == 0) atomicAdd(&skipped[0], 1);
         ok[q] = false;
       }
-      slotk[q] = ok[q] ? __shfl(slot, 16 * q + __ffs(fq) - 1) : -1;
-      rowk[q] = ok[q] ? arena + (int64_t)slotk[q] * row_width : nullptr;
+      const long long slotq = ok[q] ? __shfl(slot, PL * q + __ffs(fq) - 1) : -1;
+      rowk[q] = ok[q] ? arena + (int64_t)slotq * row_width : nullptr;
     }
-    // gradient accumulation (whole wave per key; interleaved single-position
-    // fast path is the overwhelmingly common case)
-    float acc[4][2] = {};
-    int64_t lop[4], hip[4];
+    // gradient accumulation (whole wave per key; the interleaved
+    // single-position fast path is the overwhelmingly common case)
+    // one register vector per key: a [Q][T] array is a single stack object
+    // whose runtime column index t costs more registers than Q small ones
+    PaAccVec<T> acc[Q];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      lop[q] = ok[q] ? ustarts[w * 4 + q] : 0;
-      hip[q] = ok[q] ? ustarts[w * 4 + q + 1] : 0;
+    for (int q = 0; q < Q; ++q) acc[q] = 0.0f;
+    int64_t lop[Q], hip[Q];
+    bool all_single = true;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      lop[q] = ok[q] ? ustarts[w * Q + q] : 0;
+      hip[q] = ok[q] ? ustarts[w * Q + q + 1] : 0;
+      all_single = all_single && ok[q] && hip[q] - lop[q] == 1;
     }
-    const bool all_single = ok[0] && ok[1] && ok[2] && ok[3] &&
-                            hip[0] - lop[0] == 1 && hip[1] - lop[1] == 1 &&
-                            hip[2] - lop[2] == 1 && hip[3] - lop[3] == 1;
     if (all_single) {
-      const __half* gq[4];
-      float scq[4];
+      // same rule as pa_reduce_positions: seg_id < 0 or scale 0 leaves the
+      // key's acc at 0 without multiplying its gradient (uniform per key)
+      const __half* gq[Q];
+      float scq[Q];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int q = 0; q < Q; ++q) {
         const int64_t s = seg_id[perm[lop[q]]];
         scq[q] = (s >= 0) ? (seg_scale ? seg_scale[s] : 1.0f) : 0.0f;
         gq[q] = grads + (s >= 0 ? s : 0) * dim;
       }
       for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q][t] = scq[q] * __half2float(gq[q][c]);
+        for (int q = 0; q < Q; ++q) {
+          const float g = __half2float(gq[q][c]);
+          acc[q][t] = (scq[q] != 0.0f) ? scq[q] * g : 0.0f;
+        }
       }
     } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (!ok[q]) continue;
-        for (int64_t p = lop[q]; p < hip[q]; ++p) {
-          const int64_t s = seg_id[perm[p]];
-          if (s < 0) continue;
-          const float sc = seg_scale ? seg_scale[s] : 1.0f;
-          if (sc == 0.0f) continue;
-          const __half* g = grads + s * dim;
-          for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t)
-            acc[q][t] += __half2float(g[c]) * sc;
-        }
-      }
+      for (int q = 0; q < Q; ++q)
+        if (ok[q])
+          pa_reduce_positions<T>(acc[q], grads, perm, seg_id, seg_scale,
+                                 lop[q], hip[q], dim, lane, PA_WAVE);
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < Q; ++q) {
       bool has_nan = false;
       for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t)
         has_nan |= isnan(acc[q][t]);
@@ -1153,82 +929,79 @@ __global__ void scatter_update4_kernel(
         ok[q] = false;
       }
     }
-    if (!ok[0] && !ok[1] && !ok[2] && !ok[3]) continue;
+    bool any_ok = false;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) any_ok = any_ok || ok[q];
+    if (!any_ok) continue;
+    // every branch below loads for all Q keys before the dependent math
     if (opt == 0) {  // SGD
       for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-        float w0[4];
+        float w0[Q];
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+        for (int q = 0; q < Q; ++q)
           w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < Q; ++q) {
           if (!ok[q]) continue;
-          float w2 = w0[q] - p0 * (acc[q][t] + p1 * w0[q]);
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &rowk[q][c]);
+          __builtin_nontemporal_store(pa_sgd(oa, w0[q], acc[q][t]), &rowk[q][c]);
         }
       }
     } else if (opt == 1) {  // Adagrad
-      if (p3 > 0.5f) {  // vectorwise-shared accumulator
-        float a0[4], gsq[4] = {};
+      if (pa_adagrad_shared(oa)) {
+        float a0[Q], gsq[Q] = {};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) a0[q] = ok[q] ? rowk[q][dim] : 0.0f;
+        for (int q = 0; q < Q; ++q) a0[q] = ok[q] ? rowk[q][dim] : 0.0f;
         for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-          float w0[4];
+          float w0[Q];
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
+          for (int q = 0; q < Q; ++q)
             w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
+          for (int q = 0; q < Q; ++q) {
             if (!ok[q]) continue;
-            float w2 = w0[q] - p0 * acc[q][t] * rsqrtf(a0[q] + p2);
-            if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-            __builtin_nontemporal_store(w2, &rowk[q][c]);
+            __builtin_nontemporal_store(
+                pa_adagrad_w(oa, w0[q], a0[q], acc[q][t]), &rowk[q][c]);
             gsq[q] += acc[q][t] * acc[q][t];
           }
         }
 #pragma unroll
         for (int off = PA_WAVE / 2; off > 0; off >>= 1)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) gsq[q] += __shfl_down(gsq[q], off);
+          for (int q = 0; q < Q; ++q) gsq[q] += __shfl_down(gsq[q], off);
         if (lane == 0)
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (ok[q]) rowk[q][dim] = a0[q] * p1 + gsq[q] / (float)dim;
+          for (int q = 0; q < Q; ++q)
+            if (ok[q])
+              rowk[q][dim] = pa_adagrad_shared_acc(oa, a0[q], gsq[q], dim);
       } else {
         for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-          float w0[4], a0[4];
+          float w0[Q], a0[Q];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
+          for (int q = 0; q < Q; ++q) {
             a0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][dim + c]) : 0.0f;
             w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
           }
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
+          for (int q = 0; q < Q; ++q) {
             if (!ok[q]) continue;
-            float w2 = w0[q] - p0 * acc[q][t] * rsqrtf(a0[q] + p2);
-            if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-            __builtin_nontemporal_store(w2, &rowk[q][c]);
-            __builtin_nontemporal_store(a0[q] * p1 + acc[q][t] * acc[q][t],
+            __builtin_nontemporal_store(
+                pa_adagrad_w(oa, w0[q], a0[q], acc[q][t]), &rowk[q][c]);
+            __builtin_nontemporal_store(pa_adagrad_acc(oa, a0[q], acc[q][t]),
                                         &rowk[q][dim + c]);
           }
         }
       }
     } else {  // Adam
-      const float om1 = 1.0f - p1, om2 = 1.0f - p2;
-      const float c1 = 1.0f / (1.0f - b1_power), c2 = 1.0f / (1.0f - b2_power);
       for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < Q; ++q) {
           if (!ok[q]) continue;
-          const float m =
-              p1 * __builtin_nontemporal_load(&rowk[q][dim + c]) + om1 * acc[q][t];
-          const float v = p2 * __builtin_nontemporal_load(&rowk[q][2 * dim + c]) +
-                          om2 * acc[q][t] * acc[q][t];
+          const float m = pa_adam_m(
+              oa, __builtin_nontemporal_load(&rowk[q][dim + c]), acc[q][t]);
+          const float v = pa_adam_v(
+              oa, __builtin_nontemporal_load(&rowk[q][2 * dim + c]), acc[q][t]);
           const float w0 = __builtin_nontemporal_load(&rowk[q][c]);
-          float w2 = w0 - p0 * (m * c1) / (p3 + sqrtf(v * c2));
-          if (weight_bound > 0.0f) w2 = fminf(fmaxf(w2, -weight_bound), weight_bound);
-          __builtin_nontemporal_store(w2, &rowk[q][c]);
+          __builtin_nontemporal_store(pa_adam_w(oa, w0, m, v), &rowk[q][c]);
           __builtin_nontemporal_store(m, &rowk[q][dim + c]);
           __builtin_nontemporal_store(v, &rowk[q][2 * dim + c]);
         }
@@ -1251,6 +1024,15 @@ inline int n_blocks_for(int64_t work_items, int per_block) {
 
 static hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
+}
+
+// optional tensor arguments arrive empty when absent
+static const long long* count_or_null(const torch::Tensor& u_count) {
+  return u_count.numel() ? (const long long*)u_count.data_ptr<int64_t>()
+                         : nullptr;
+}
+static const float* scale_or_null(const torch::Tensor& seg_scale) {
+  return seg_scale.numel() ? seg_scale.data_ptr<float>() : nullptr;
 }
 
 // u64 radix sort-pairs (keys ascending in UNSIGNED order — exactly the
@@ -1307,8 +1089,7 @@ void store_lookup(torch::Tensor table_keys, torch::Tensor ticks,
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)(dim + opt_space);
   const bool spill = evict_keys.numel() > 0;
-  const long long* n_dev =
-      u_count.numel() ? (const long long*)u_count.data_ptr<int64_t>() : nullptr;
+  const long long* n_dev = count_or_null(u_count);
   auto opts = torch::TensorOptions().dtype(torch::kInt64).device(query.device());
   auto slots = torch::empty({n}, opts);
   auto is_new = torch::empty({n}, opts.dtype(torch::kInt32));
@@ -1362,8 +1143,7 @@ void store_lookup_sums(torch::Tensor table_keys, torch::Tensor ticks,
   if (n == 0) return;
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)(dim + opt_space);
-  const long long* n_dev =
-      u_count.numel() ? (const long long*)u_count.data_ptr<int64_t>() : nullptr;
+  const long long* n_dev = count_or_null(u_count);
   auto opts = torch::TensorOptions().dtype(torch::kInt64).device(query.device());
   auto slots = torch::empty({n}, opts);
   auto is_new = torch::empty({n}, opts.dtype(torch::kInt32));
@@ -1417,9 +1197,7 @@ torch::Tensor store_probe(torch::Tensor table_keys, torch::Tensor ticks,
                      /*train=*/0, (unsigned)tick, 1.0f,
                      (long long*)slots.data_ptr<int64_t>(),
                      is_new.data_ptr<int32_t>(), nullptr, nullptr, nullptr,
-                     u_count.numel()
-                         ? (const long long*)u_count.data_ptr<int64_t>()
-                         : nullptr);
+                     count_or_null(u_count));
   return slots;
 }
 
@@ -1474,8 +1252,7 @@ torch::Tensor segment_sum(torch::Tensor rows, torch::Tensor inverse,
       {n_seg, dim},
       torch::TensorOptions().dtype(torch::kFloat16).device(rows.device()));
   if (n_seg == 0) return out;
-  const float* scale_ptr =
-      seg_scale.numel() ? seg_scale.data_ptr<float>() : nullptr;
+  const float* scale_ptr = scale_or_null(seg_scale);
   hipStream_t st = cur_stream();
   const dim3 grid(n_blocks_for(n_seg, 4)), block(256);
   if (rows.scalar_type() == torch::kFloat32) {
@@ -1504,8 +1281,7 @@ void grad_scatter(torch::Tensor grads, torch::Tensor perm,
   if (n_unique == 0) return;
   hipStream_t st = cur_stream();
   const dim3 grid(n_blocks_for(n_unique, 4)), block(256);
-  const float* scale_ptr =
-      seg_scale.numel() ? seg_scale.data_ptr<float>() : nullptr;
+  const float* scale_ptr = scale_or_null(seg_scale);
 #define PA_GS(T, ACC)                                                         \
   hipLaunchKernelGGL((grad_scatter_kernel<T, ACC>), grid, block, 0, st,       \
                      (const T*)grads.data_ptr(), perm.data_ptr<int64_t>(),    \
@@ -1535,10 +1311,8 @@ void grad_scatter_idx(torch::Tensor grads, torch::Tensor perm,
               "grad_scatter_idx: f16 grads");
   hipStream_t st = cur_stream();
   const dim3 grid(n_blocks_for(n_unique, 4)), block(256);
-  const float* scale_ptr =
-      seg_scale.numel() ? seg_scale.data_ptr<float>() : nullptr;
-  const long long* n_dev =
-      u_count.numel() ? (const long long*)u_count.data_ptr<int64_t>() : nullptr;
+  const float* scale_ptr = scale_or_null(seg_scale);
+  const long long* n_dev = count_or_null(u_count);
   if (out.scalar_type() == torch::kFloat16) {
     hipLaunchKernelGGL(grad_scatter_idx_kernel<__half>, grid, block, 0, st,
                        (const __half*)grads.data_ptr<at::Half>(),
@@ -1573,66 +1347,34 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
   TORCH_CHECK(dim <= 8 * PA_WAVE, "scatter_update: dim too large");
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)arena.size(1);
-  const float* scale_ptr =
-      seg_scale.numel() ? seg_scale.data_ptr<float>() : nullptr;
-  // full-wave dims: dual-key variant (2x memory-level parallelism); small
-  // dividing dims keep the sub-wave-packed single kernel (more keys/wave)
+  // the three variants share one signature: launch `kernel` with one wave
+  // per `keys_per_wave` unique keys
+  auto launch = [&](auto kernel, int keys_per_wave) {
+    const int64_t waves = (n + keys_per_wave - 1) / keys_per_wave;
+    hipLaunchKernelGGL(kernel, dim3(n_blocks_for(waves, 4)), dim3(256), 0,
+                       cur_stream(), (ull*)table_keys.data_ptr<int64_t>(),
+                       (unsigned*)ticks.data_ptr<int32_t>(),
+                       arena.data_ptr<float>(),
+                       (const ull*)uniq.data_ptr<int64_t>(),
+                       (const __half*)grads.data_ptr<at::Half>(),
+                       perm.data_ptr<int64_t>(), ustarts.data_ptr<int64_t>(),
+                       seg_id.data_ptr<int64_t>(), scale_or_null(seg_scale), n,
+                       (int)dim, row_width, n_buckets, (int)opt,
+                       (float)params[0], (float)params[1], (float)params[2],
+                       (float)params[3], (float)b1_power, (float)b2_power,
+                       (float)weight_bound, skipped.data_ptr<int32_t>(),
+                       count_or_null(u_count));
+  };
+  // small dividing dims keep the sub-wave-packed kernel (more keys per
+  // wave); other dims take as many keys per wave as the register-resident
+  // gradient allows (memory-level parallelism), down to one above 256
   const bool packed_small = (dim < PA_WAVE && (PA_WAVE % dim) == 0);
-  if (!packed_small && dim <= 128) {
-    hipLaunchKernelGGL(scatter_update4_kernel,
-                       dim3(n_blocks_for((n + 3) / 4, 4)), dim3(256), 0,
-                       cur_stream(), (ull*)table_keys.data_ptr<int64_t>(),
-                       (unsigned*)ticks.data_ptr<int32_t>(),
-                       arena.data_ptr<float>(),
-                       (const ull*)uniq.data_ptr<int64_t>(),
-                       (const __half*)grads.data_ptr<at::Half>(),
-                       perm.data_ptr<int64_t>(), ustarts.data_ptr<int64_t>(),
-                       seg_id.data_ptr<int64_t>(), scale_ptr, n, (int)dim,
-                       row_width, n_buckets, (int)opt, (float)params[0],
-                       (float)params[1], (float)params[2], (float)params[3],
-                       (float)b1_power, (float)b2_power, (float)weight_bound,
-                       skipped.data_ptr<int32_t>(),
-                       u_count.numel()
-                           ? (const long long*)u_count.data_ptr<int64_t>()
-                           : nullptr);
-    return;
-  }
-  const bool dual = !packed_small && dim <= 256;
-  if (dual) {
-    hipLaunchKernelGGL(scatter_update2_kernel,
-                       dim3(n_blocks_for((n + 1) / 2, 4)), dim3(256), 0,
-                       cur_stream(), (ull*)table_keys.data_ptr<int64_t>(),
-                       (unsigned*)ticks.data_ptr<int32_t>(),
-                       arena.data_ptr<float>(),
-                       (const ull*)uniq.data_ptr<int64_t>(),
-                       (const __half*)grads.data_ptr<at::Half>(),
-                       perm.data_ptr<int64_t>(), ustarts.data_ptr<int64_t>(),
-                       seg_id.data_ptr<int64_t>(), scale_ptr, n, (int)dim,
-                       row_width, n_buckets, (int)opt, (float)params[0],
-                       (float)params[1], (float)params[2], (float)params[3],
-                       (float)b1_power, (float)b2_power, (float)weight_bound,
-                       skipped.data_ptr<int32_t>(),
-                       u_count.numel()
-                           ? (const long long*)u_count.data_ptr<int64_t>()
-                           : nullptr);
-    return;
-  }
-  hipLaunchKernelGGL(scatter_update_kernel, dim3(n_blocks_for(n, 4)),
-                     dim3(256), 0, cur_stream(),
-                     (ull*)table_keys.data_ptr<int64_t>(),
-                     (unsigned*)ticks.data_ptr<int32_t>(),
-                     arena.data_ptr<float>(),
-                     (const ull*)uniq.data_ptr<int64_t>(),
-                     (const __half*)grads.data_ptr<at::Half>(),
-                     perm.data_ptr<int64_t>(), ustarts.data_ptr<int64_t>(),
-                     seg_id.data_ptr<int64_t>(), scale_ptr, n, (int)dim,
-                     row_width, n_buckets, (int)opt, (float)params[0],
-                     (float)params[1], (float)params[2], (float)params[3],
-                     (float)b1_power, (float)b2_power, (float)weight_bound,
-                     skipped.data_ptr<int32_t>(),
-                     u_count.numel()
-                         ? (const long long*)u_count.data_ptr<int64_t>()
-                         : nullptr);
+  if (!packed_small && dim <= 128)
+    launch(scatter_update_multi_kernel<4>, 4);
+  else if (!packed_small && dim <= 256)
+    launch(scatter_update_multi_kernel<2>, 2);
+  else
+    launch(scatter_update_kernel, 1);
 }
 
 // -> (send [world*cap+1] zero-padded, idx [n_pad]); overflow accumulates
@@ -1646,8 +1388,7 @@ std::vector<torch::Tensor> a2a_route(torch::Tensor uniq, torch::Tensor u_count,
   auto idx = torch::empty({n_pad}, opts);
   auto starts = torch::empty({world + 1}, opts);
   hipStream_t st = cur_stream();
-  const long long* n_dev =
-      u_count.numel() ? (const long long*)u_count.data_ptr<int64_t>() : nullptr;
+  const long long* n_dev = count_or_null(u_count);
   hipLaunchKernelGGL(a2a_bounds_kernel, dim3(1), dim3(world + 1), 0, st,
                      (const ull*)uniq.data_ptr<int64_t>(), n_dev, n_pad,
                      (int)world, (long long*)starts.data_ptr<int64_t>());

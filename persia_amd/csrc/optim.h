@@ -1,0 +1,123 @@
+// Row-wise sparse optimizer math and the ordered gradient reduction — the one
+// copy every update kernel in kernels.hip calls.
+//
+// The optimizer functions are pure register math, one element at a time:
+// they take the loaded values and return the new ones, so each kernel keeps
+// its own load / compute / store interleaving (the multi-key kernels issue
+// the loads of all their keys before the dependent math).  The expressions
+// are exact-math variants of the reference (persia-simd lib.rs:21-251); every
+// kernel inlines the same expression tree, so they contract identically.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+#include <cstdint>
+
+#include "common.h"
+
+__device__ __forceinline__ float pa_to_float(float x) { return x; }
+__device__ __forceinline__ float pa_to_float(__half x) { return __half2float(x); }
+__device__ __forceinline__ float pa_to_float(__hip_bfloat16 x) {
+  return __bfloat162float(x);
+}
+
+// opt: 0 = SGD      p0=lr p1=weight_decay
+//      1 = Adagrad  p0=lr p1=g_square_momentum p2=eps p3=vectorwise_shared
+//      2 = Adam     p0=lr p1=beta1 p2=beta2 p3=eps      (store.py _opt_params)
+struct PaOptArgs {
+  int opt;
+  float p0, p1, p2, p3;
+  float weight_bound;
+  float om1, om2, c1, c2;  // Adam: 1-beta, 1/(1-beta^t)
+};
+
+__device__ __forceinline__ PaOptArgs pa_opt_args(int opt, float p0, float p1,
+                                                 float p2, float p3,
+                                                 float b1_power, float b2_power,
+                                                 float weight_bound) {
+  PaOptArgs a;
+  a.opt = opt;
+  a.p0 = p0; a.p1 = p1; a.p2 = p2; a.p3 = p3;
+  a.weight_bound = weight_bound;
+  a.om1 = 1.0f - p1;
+  a.om2 = 1.0f - p2;
+  a.c1 = 1.0f / (1.0f - b1_power);
+  a.c2 = 1.0f / (1.0f - b2_power);
+  return a;
+}
+
+__device__ __forceinline__ bool pa_adagrad_shared(const PaOptArgs& a) {
+  return a.p3 > 0.5f;
+}
+
+__device__ __forceinline__ float pa_clamp_weight(const PaOptArgs& a, float w) {
+  if (a.weight_bound > 0.0f) w = fminf(fmaxf(w, -a.weight_bound), a.weight_bound);
+  return w;
+}
+
+// SGD: w -= lr*(g + wd*w)
+__device__ __forceinline__ float pa_sgd(const PaOptArgs& a, float w, float g) {
+  return pa_clamp_weight(a, w - a.p0 * (g + a.p1 * w));
+}
+
+// Adagrad weight step; acc is the column's accumulator, or the row's one
+// scalar accumulator when vectorwise-shared
+__device__ __forceinline__ float pa_adagrad_w(const PaOptArgs& a, float w,
+                                              float acc, float g) {
+  return pa_clamp_weight(a, w - a.p0 * g * rsqrtf(acc + a.p2));
+}
+
+// Adagrad state step, per column
+__device__ __forceinline__ float pa_adagrad_acc(const PaOptArgs& a, float acc,
+                                                float g) {
+  return acc * a.p1 + g * g;
+}
+
+// Adagrad state step, vectorwise-shared: gsq = sum of g*g over the row
+__device__ __forceinline__ float pa_adagrad_shared_acc(const PaOptArgs& a,
+                                                       float acc, float gsq,
+                                                       int dim) {
+  return acc * a.p1 + gsq / (float)dim;
+}
+
+// Adam moment steps, then the weight step from the NEW moments
+__device__ __forceinline__ float pa_adam_m(const PaOptArgs& a, float m, float g) {
+  return a.p1 * m + a.om1 * g;
+}
+__device__ __forceinline__ float pa_adam_v(const PaOptArgs& a, float v, float g) {
+  return a.p2 * v + a.om2 * g * g;
+}
+__device__ __forceinline__ float pa_adam_w(const PaOptArgs& a, float w, float m,
+                                           float v) {
+  return pa_clamp_weight(a, w - a.p0 * (m * a.c1) / (a.p3 + sqrtf(v * a.c2)));
+}
+
+// Ordered gradient reduction of one unique key: accumulate its positions
+// [lo, hi) (contiguous in sort order) into acc[t] for the lane's columns
+// c0, c0+st, ... < dim.  A position with seg_id < 0 (raw-slot positions,
+// handled by a separate indexed add) or seg_scale == 0 (NaN-slot mask)
+// contributes nothing: its gradient is neither read nor multiplied — never
+// multiply a NaN gradient, even by zero.  Null seg_scale = 1.  acc is any
+// T-element accumulator indexable by [t]; T == 1 is the one-column form (st
+// unused).
+template <int T, typename AccT, typename GradT>
+__device__ __forceinline__ void pa_reduce_positions(
+    AccT& acc, const GradT* __restrict__ grads,
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ seg_id,
+    const float* __restrict__ seg_scale, int64_t lo, int64_t hi, int dim,
+    int c0, int st) {
+  for (int64_t p = lo; p < hi; ++p) {
+    const int64_t s = seg_id[perm[p]];
+    if (s < 0) continue;
+    const float sc = seg_scale ? seg_scale[s] : 1.0f;
+    if (sc == 0.0f) continue;
+    const GradT* g = grads + s * dim;
+    if constexpr (T == 1) {
+      acc[0] += pa_to_float(g[c0]) * sc;
+    } else {
+      for (int t = 0, c = c0; c < dim; c += st, ++t)
+        acc[t] += pa_to_float(g[c]) * sc;
+    }
+  }
+}

@@ -19,25 +19,39 @@ def _keys(signs):
     return torch.from_numpy(h.view(np.int64))
 
 
-def _cpu_store(opt=None, capacity=4096, dim=8):
+def _cpu_store(opt=None, capacity=4096, dim=8, **hyper):
     from persia_amd.core.store import CpuEmbeddingStore
     from persia_amd.embedding import EmbeddingConfig
     from persia_amd.embedding.optim import SGD
 
     return CpuEmbeddingStore(
-        dim, capacity, opt or SGD(lr=0.1), EmbeddingConfig(emb_initialization=(-0.5, 0.5))
+        dim, capacity, opt or SGD(lr=0.1),
+        EmbeddingConfig(emb_initialization=(-0.5, 0.5), **hyper),
     )
 
 
-def _hip_store(opt=None, capacity=4096, dim=8):
+def _hip_store(opt=None, capacity=4096, dim=8, **hyper):
     from persia_amd.core.store import HipEmbeddingStore
     from persia_amd.embedding import EmbeddingConfig
     from persia_amd.embedding.optim import SGD
 
     return HipEmbeddingStore(
-        dim, capacity, opt or SGD(lr=0.1), EmbeddingConfig(emb_initialization=(-0.5, 0.5)),
+        dim, capacity, opt or SGD(lr=0.1),
+        EmbeddingConfig(emb_initialization=(-0.5, 0.5), **hyper),
         _dev(),
     )
+
+
+def _mk_opt(optname):
+    from persia_amd.embedding.optim import SGD, Adagrad, Adam
+
+    if optname == "sgd":
+        return SGD(lr=0.1, weight_decay=0.01)
+    if optname == "adagrad":
+        return Adagrad(lr=0.1, initial_accumulator_value=0.01, g_square_momentum=0.9)
+    if optname == "adagrad_shared":
+        return Adagrad(lr=0.1, initial_accumulator_value=0.01, vectorwise_shared=True)
+    return Adam(lr=0.01)
 
 
 def test_native_loaded():
@@ -73,19 +87,8 @@ def test_store_infer_miss_zeros():
 
 @pytest.mark.parametrize("optname", ["sgd", "adagrad", "adagrad_shared", "adam"])
 def test_store_update_matches_cpu_oracle(optname):
-    from persia_amd.embedding.optim import SGD, Adagrad, Adam
-
-    def mk():
-        if optname == "sgd":
-            return SGD(lr=0.1, weight_decay=0.01)
-        if optname == "adagrad":
-            return Adagrad(lr=0.1, initial_accumulator_value=0.01, g_square_momentum=0.9)
-        if optname == "adagrad_shared":
-            return Adagrad(lr=0.1, initial_accumulator_value=0.01, vectorwise_shared=True)
-        return Adam(lr=0.01)
-
-    cpu = _cpu_store(mk())
-    hip = _hip_store(mk())
+    cpu = _cpu_store(_mk_opt(optname))
+    hip = _hip_store(_mk_opt(optname))
     signs = list(range(1, 64))
     k = _keys(signs)
     cpu.lookup(k, train=True)
@@ -373,11 +376,14 @@ def test_engine_gpu_matches_cpu_engine():
         gpu_eng.apply_gradients(tb_g, gg)
 
 
-@pytest.mark.parametrize("dim", [16, 128])
+@pytest.mark.parametrize("dim", [16, 24, 128])
 def test_fused_scatter_update_matches_cpu(dim):
-    """apply_gradients_base single-GPU fast path (fused scatter_update
-    kernel; dim=16 exercises the sub-wave-packed kernel, dim=128 the
-    dual-key full-wave kernel) vs the CPU oracle engine."""
+    """apply_gradients_base single-GPU fast path vs the CPU oracle engine.
+    Backward: the fused scatter_update — dim=16 takes the sub-wave-packed
+    kernel, dim=24 and dim=128 the four-keys-per-wave kernel.  Forward:
+    store_lookup_sums — dim=16 takes init_scatter, dim=24 and dim=128 the
+    dual-key init_scatter2; the first batch sees only fresh rows, so its f16
+    sums pin the seeded row init bitwise."""
     from persia_amd.core.comm import DistContext
     from persia_amd.core.engine import EmbeddingEngine
     from persia_amd.core.schema import EmbeddingSchema, GlobalConfig, SlotConfig
@@ -412,6 +418,9 @@ def test_fused_scatter_update_matches_cpu(dim):
     for step in range(3):
         tb_c = cpu.process_batch(batch(step))
         tb_g = gpu.process_batch(batch(step))
+        if step == 0:  # fresh rows only, no update applied yet
+            for pc, pg in zip(tb_c.payloads, tb_g.payloads):
+                assert torch.equal(pc.sum_tensor, pg.sum_tensor.cpu()), pc.name
         g = torch.randn(3 * 32, dim).to(torch.float16)
         tb_c.enable_training_views()
         tb_g.enable_training_views()
@@ -424,6 +433,203 @@ def test_fused_scatter_update_matches_cpu(dim):
     for pc, pg in zip(t_c.payloads, t_g.payloads):
         assert torch.allclose(pc.sum_tensor.float(), pg.sum_tensor.cpu().float(),
                               atol=2e-3, rtol=1e-3), pc.name
+
+
+# ---- scatter_update called directly: every kernel variant x every optimizer
+
+# dim -> variant: 16 packed (4 keys/wave); 24 (lanes >= dim idle), 64, 128
+# (two columns per lane) four keys per wave; 192 (ragged third column), 256
+# two keys per wave; 320 (ragged), 512 (the limit) one key per wave
+_FUSED_DIMS = [16, 24, 64, 128, 192, 256, 320, 512]
+_FUSED_OPTS = ["sgd", "adagrad", "adagrad_shared", "adam"]
+# (dim, optimizer) cases where the fused kernel and grad_scatter+store_update
+# were not bit-equal before the optimizer math was single-sourced, so they
+# keep the oracle tolerance instead of torch.equal.  The source expression
+# is the same everywhere; in the per-column Adagrad state step
+# acc*p1 + g*g the compiler fuses one product or the other into the add
+# depending on the surrounding kernel, a last-ulp difference.
+_FUSED_VS_FALLBACK_TOL = {(d, "adagrad") for d in (16, 192, 256, 320, 512)}
+
+_N_UNIQ, _N_PAD = 11, 16
+_U_MULTI, _U_MISSING, _U_NAN = 1, 2, 7
+
+
+def _fused_bound(dim):
+    # the clamp bites (init is +-0.5, steps are O(0.1..1)) on one dim per
+    # kernel variant, for every optimizer; the other dims run without a bound
+    return 0.3 if dim in (16, 128, 256, 320) else 0.0
+
+
+_fused_cache = {}
+
+
+def _fused_case(dim):
+    """Inputs of one fused scatter+update call, built once per dim and shared
+    read-only: 11 unique keys, padded to 16 with the empty key and counted by
+    a device-side u_count, so the last wave is partial at 2 and at 4 keys per
+    wave.  Key 1 has three positions (generic reduction branch in its wave;
+    keys 4..7 and 8..9 form waves that take the all-single fast path), key 2
+    was never looked up (miss), key 7's gradient holds a NaN (row skip).
+    Scales are powers of two, so every f16*scale product is exact and the
+    ordered f32 sum below is the kernels' reduction bit for bit."""
+    if dim in _fused_cache:
+        return _fused_cache[dim]
+    g = torch.Generator().manual_seed(1000 + dim)
+    signs = np.arange(1, _N_UNIQ + 1, dtype=np.uint64)
+    keys = _keys(signs)
+    npos = torch.ones(_N_UNIQ, dtype=torch.int64)
+    npos[_U_MULTI] = 3
+    nnz = int(npos.sum())
+    ustarts = torch.zeros(_N_UNIQ + 1, dtype=torch.int64)
+    ustarts[1:] = torch.cumsum(npos, 0)
+    perm = torch.randperm(nnz, generator=g)    # sorted position -> position
+    seg_id = torch.randperm(nnz, generator=g)  # position -> gradient row
+    seg_scale = torch.tensor([1.0, 0.5, 0.25, 2.0])[
+        torch.randint(0, 4, (nnz,), generator=g)
+    ]
+    grads = torch.randn(nnz, dim, generator=g).to(torch.float16)
+    grads[seg_id[perm[ustarts[_U_NAN]]], dim // 2] = float("nan")
+    reduced = torch.zeros(_N_UNIQ, dim)
+    for u in range(_N_UNIQ):
+        for p in range(int(ustarts[u]), int(ustarts[u + 1])):
+            s = seg_id[perm[p]]
+            reduced[u] = reduced[u] + grads[s].float() * seg_scale[s]
+    dev = _dev()
+    pad = _N_PAD - _N_UNIQ
+    case = dict(
+        dim=dim, signs=signs, keys=keys, reduced=reduced,
+        looked_up=torch.cat([keys[:_U_MISSING], keys[_U_MISSING + 1:]]),
+        keys_d=keys.to(dev),
+        uniq_pad=torch.cat([keys, torch.zeros(pad, dtype=torch.int64)]).to(dev),
+        ustarts_d=ustarts.to(dev),
+        ustarts_pad=torch.cat([ustarts, torch.full((pad,), nnz)]).to(dev),
+        perm=perm.to(dev), seg_id=seg_id.to(dev), seg_scale=seg_scale.to(dev),
+        grads=grads.to(dev),
+        u_count=torch.tensor([_N_UNIQ], dtype=torch.int64, device=dev),
+    )
+    _fused_cache[dim] = case
+    return case
+
+
+def _scatter_update(store, uniq, grads, perm, ustarts, seg_id, seg_scale, u_count):
+    """The engine's fused-backward call (engine.py _a2a_backward_native)."""
+    from persia_amd.ops import native
+
+    powers = store._adam_step_powers()
+    b1p, b2p = powers if powers else (0.0, 0.0)
+    native().scatter_update(
+        store.keys, store.ticks, store.arena, uniq, grads, perm, ustarts,
+        seg_id, seg_scale, store.dim, store._opt_code, store._opt_params(),
+        float(b1p), float(b2p), float(store.hyper.weight_bound),
+        store._skipped, u_count,
+    )
+
+
+def _fused_step(store, case):
+    _scatter_update(
+        store, case["uniq_pad"], case["grads"], case["perm"],
+        case["ustarts_pad"], case["seg_id"], case["seg_scale"], case["u_count"],
+    )
+
+
+@pytest.mark.parametrize("optname", _FUSED_OPTS)
+@pytest.mark.parametrize("dim", _FUSED_DIMS)
+def test_scatter_update_matches_cpu_oracle(dim, optname):
+    case = _fused_case(dim)
+    wb = _fused_bound(dim)
+    cpu = _cpu_store(_mk_opt(optname), dim=dim, weight_bound=wb)
+    hip = _hip_store(_mk_opt(optname), dim=dim, weight_bound=wb)
+    cpu.lookup(case["looked_up"], train=True)
+    hip.lookup(case["looked_up"].to(_dev()), train=True)
+    nan_sign = case["signs"][_U_NAN : _U_NAN + 1]
+    nan_row_before = hip.export_keys(nan_sign)[1]
+
+    assert cpu.update_gradients(case["keys"], case["reduced"]) == 1
+    _fused_step(hip, case)
+
+    # one miss, one NaN row; the padding keys count as neither
+    assert hip._skipped.tolist() == [1, 1]
+    assert np.array_equal(hip.export_keys(nan_sign)[1], nan_row_before)
+    s_c, r_c = cpu.export_keys(case["signs"])
+    s_h, r_h = hip.export_keys(case["signs"])
+    assert np.array_equal(s_c, s_h) and len(s_h) == _N_UNIQ - 1
+    # whole rows: weights and optimizer state.  GPU rsqrtf vs torch rsqrt can
+    # differ in the last ulp
+    assert np.allclose(r_c, r_h, atol=1e-5, rtol=1e-5), (
+        f"max diff {np.abs(r_c - r_h).max()}"
+    )
+
+
+@pytest.mark.parametrize("optname", _FUSED_OPTS)
+@pytest.mark.parametrize("dim", _FUSED_DIMS)
+def test_scatter_update_matches_fallback_path(dim, optname):
+    """Fused scatter_update vs grad_scatter (f32 out) + store_update on a twin
+    store: same reduction, same optimizer math, so the same bits."""
+    from persia_amd.ops import native
+
+    case = _fused_case(dim)
+    wb = _fused_bound(dim)
+    fused = _hip_store(_mk_opt(optname), dim=dim, weight_bound=wb)
+    twin = _hip_store(_mk_opt(optname), dim=dim, weight_bound=wb)
+    for st in (fused, twin):
+        st.lookup(case["looked_up"].to(_dev()), train=True)
+    assert torch.equal(fused.arena, twin.arena)
+
+    _fused_step(fused, case)
+    red = torch.empty(_N_UNIQ, dim, device=_dev())
+    native().grad_scatter(
+        case["grads"], case["perm"], case["ustarts_d"], case["seg_id"],
+        case["seg_scale"], red, 0,
+    )
+    twin.update_gradients(case["keys_d"], red)
+
+    assert torch.equal(fused.keys, twin.keys)
+    assert torch.equal(fused._skipped, twin._skipped)
+    if (dim, optname) in _FUSED_VS_FALLBACK_TOL:
+        assert torch.allclose(fused.arena, twin.arena, atol=1e-5, rtol=1e-5)
+    else:
+        assert torch.equal(fused.arena, twin.arena)
+
+
+@pytest.mark.parametrize("optname", ["sgd", "adagrad"])
+@pytest.mark.parametrize("dim", [16, 128])
+def test_scatter_update_zero_scale_never_touches_gradient(dim, optname):
+    """A segment scaled by 0 (the NaN-slot mask) contributes nothing, on
+    every path: its NaN gradient must not reach the row or the NaN counter.
+    Four single-position keys: one wave of the packed kernel at dim 16, the
+    all-single fast path of the four-keys-per-wave kernel at dim 128."""
+    dev = _dev()
+    g = torch.Generator().manual_seed(2000 + dim)
+    signs = np.arange(1, 5, dtype=np.uint64)
+    keys = _keys(signs)
+    perm = torch.randperm(4, generator=g)
+    seg_id = torch.randperm(4, generator=g)
+    seg_scale = torch.tensor([1.0, 0.0, 1.0, 1.0])
+    grads = torch.randn(4, dim, generator=g).to(torch.float16)
+    grads[1] = float("nan")
+    reduced = torch.zeros(4, dim)
+    for u in range(4):
+        s = seg_id[perm[u]]
+        if seg_scale[s] != 0:
+            reduced[u] = grads[s].float() * seg_scale[s]
+
+    cpu = _cpu_store(_mk_opt(optname), dim=dim)
+    hip = _hip_store(_mk_opt(optname), dim=dim)
+    cpu.lookup(keys, train=True)
+    hip.lookup(keys.to(dev), train=True)
+    assert cpu.update_gradients(keys, reduced) == 0
+    _scatter_update(
+        hip, keys.to(dev), grads.to(dev), perm.to(dev),
+        torch.arange(5, device=dev), seg_id.to(dev), seg_scale.to(dev),
+        torch.empty(0, dtype=torch.int64, device=dev),
+    )
+    assert hip._skipped.tolist() == [0, 0]
+    r_c = cpu.export_keys(signs)[1]
+    r_h = hip.export_keys(signs)[1]
+    assert r_h.shape == r_c.shape
+    assert np.allclose(r_c, r_h, atol=1e-5, rtol=1e-5), (
+        f"max diff {np.abs(r_c - r_h).max()}"
+    )
 
 
 def test_checkpoint_gpu_roundtrip(tmp_path):
