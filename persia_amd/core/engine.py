@@ -24,6 +24,9 @@ Per batch (one dim-group):
   6. backward: reverse — segment grad scatter, all_to_all, fused
      optimizer update on the owner shard.
 """
+import contextlib
+import functools
+import os
 import queue
 import threading
 import time
@@ -46,12 +49,12 @@ from persia_amd.ops import reference as R
 _logger = get_default_logger("persia_amd.engine")
 
 _FLIP = -(2 ** 63)  # XOR with sign bit: signed sort order == unsigned order
+_NO_STREAM = contextlib.nullcontext()  # stands in for torch.cuda.stream(...)
 
 
 def _roctx_range(name):
     """Method decorator: named roctx range (rocprofv3 --marker-trace) when
     the engine runs with PA_ROCTX=1; a bare call otherwise."""
-    import functools
 
     def deco(fn):
         @functools.wraps(fn)
@@ -65,6 +68,47 @@ def _roctx_range(name):
                 torch.cuda.nvtx.range_pop()
         return wrap
     return deco
+
+
+def _update_entry(fn):
+    """Decorator of the two public gradient entry points: advances
+    ``_update_counter`` once per call, samples the host-side issue+wait time
+    of the whole push into ``update_gradient_time_cost_sec`` (the reference's
+    gauge, mod.rs:83-100) every PA_METRICS_EVERY calls, and opens the
+    ``persia:update`` roctx range under PA_ROCTX=1."""
+
+    @functools.wraps(fn)
+    def wrap(self, *a, **k):
+        self._update_counter += 1
+        sample = (
+            self.metrics_enabled
+            and self._update_counter % self._metrics_every
+            == 1 % self._metrics_every
+        )
+        if not (sample or self._roctx):
+            return fn(self, *a, **k)
+        if self._roctx:
+            torch.cuda.nvtx.range_push("persia:update")
+        t0 = time.perf_counter()
+        try:
+            return fn(self, *a, **k)
+        finally:
+            if sample:
+                self.metrics.update_gradient_time_cost_sec.set(
+                    time.perf_counter() - t0
+                )
+            if self._roctx:
+                torch.cuda.nvtx.range_pop()
+
+    return wrap
+
+
+def _sqrt_scale(sqrt_mask: torch.Tensor, seg_lens: torch.Tensor) -> torch.Tensor:
+    """Per-segment 1/sqrt(len) of the sqrt-scaling sum slots (1 elsewhere):
+    the forward sum and its gradient carry the same factor."""
+    return torch.where(
+        sqrt_mask, seg_lens.clamp(min=1.0).rsqrt(), torch.ones_like(seg_lens)
+    )
 
 
 def _owner_of_keys(keys: torch.Tensor, world_size: int) -> torch.Tensor:
@@ -165,13 +209,14 @@ class _GroupPlan:
     fast path (the DLRM shape: every slot one id per sample).  Everything here
     is shape-derived, so one plan serves every batch of that shape."""
 
-    def __init__(self, dim: int, names, prefixes_np: np.ndarray, B: int,
+    def __init__(self, dim: int, cfgs: List[SlotConfig], B: int,
                  device: torch.device):
-        S = len(names)
+        S = len(cfgs)
         self.dim = dim
-        self.names = names
+        self.names = tuple(c.name for c in cfgs)
         self.B = B
         self.S = S
+        prefixes_np = np.array([c.index_prefix for c in cfgs], dtype=np.uint64)
         self.slot_starts = torch.arange(0, (S + 1) * B, B, dtype=torch.int64,
                                         device=device)
         self.prefixes = torch.from_numpy(prefixes_np.view(np.int64)).to(device)
@@ -347,15 +392,13 @@ class EmbeddingEngine:
         self.skipped_grad_signs = 0
         self.nan_grad_batches = 0
         self._plans = {}
-        self._empty_scale = None
-        self._empty_count = None
-        self._pin_rings: Dict[int, list] = {}
-        self._pin_idx: Dict[int, int] = {}
+        self._empty_scale = torch.empty(0, dtype=torch.float32, device=device)
+        spacing = schema.feature_spacing
+        self._spacing_arg = spacing if spacing < (1 << 63) else -1
         self.model_manager_status = "Idle"
         self.model_manager_progress = 0.0
-        import os as _os
-
-        self._prod_timing = _os.environ.get("PA_PROD_TIMING", "0") == "1"
+        self._prod_timing = os.environ.get("PA_PROD_TIMING", "0") == "1"
+        self._prod_timing_live = True  # cleared while the warm-up skip runs
         # timers skip the first batches: one-time ATen kernel-module loads
         # (~hundreds of ms) otherwise dominate the averages
         self._pt = {"prep": 0.0, "native": 0.0, "batch": 0.0, "n": 0,
@@ -364,12 +407,12 @@ class EmbeddingEngine:
         # PA_FUSED_DIST=0 falls back to the exact two-phase counts exchange,
         # PA_FORCE_DIST=1 exercises the padded machinery at world_size=1
         # (copy in place of the collectives) for single-GPU tests/profiling
-        self._fused_dist = _os.environ.get("PA_FUSED_DIST", "1") == "1"
-        self._force_dist = _os.environ.get("PA_FORCE_DIST", "0") == "1"
+        self._fused_dist = os.environ.get("PA_FUSED_DIST", "1") == "1"
+        self._force_dist = os.environ.get("PA_FORCE_DIST", "0") == "1"
         # PA_ROCTX=1: named roctx ranges around the pipeline stages for
         # rocprofv3 --marker-trace (torch.cuda.nvtx IS roctx on ROCm);
         # off by default so the hot loop never pays the marker calls
-        self._roctx = _os.environ.get("PA_ROCTX", "0") == "1"
+        self._roctx = os.environ.get("PA_ROCTX", "0") == "1"
         self._a2a_overflow = torch.zeros(1, dtype=torch.int64, device=device)
         from persia_amd.core.metrics import EngineMetrics
 
@@ -379,7 +422,7 @@ class EmbeddingEngine:
         # the flagship loop never pays for timers/copies it does not use;
         # GPU-side values (event timings, device counters) are harvested one
         # sample late through pinned async copies — no stream syncs
-        self._metrics_every = max(1, int(_os.environ.get("PA_METRICS_EVERY", "64")))
+        self._metrics_every = max(1, int(os.environ.get("PA_METRICS_EVERY", "64")))
         self._batch_counter = 0
         self._update_counter = 0
         self._pending_metric = None
@@ -408,15 +451,22 @@ class EmbeddingEngine:
         self.incremental = IncrementalUpdateDumper(self, dst_dir, buffer_size)
         return self.incremental
 
-    def _empty_f32(self) -> torch.Tensor:
-        if self._empty_scale is None:
-            self._empty_scale = torch.empty(0, dtype=torch.float32, device=self.device)
-        return self._empty_scale
+    @functools.cached_property
+    def _C(self):
+        """The HIP extension, imported on first use: CPU-only hosts import
+        this module (and run the CPU engine) without it."""
+        from persia_amd.ops import native
 
-    def _empty_i64(self) -> torch.Tensor:
-        if self._empty_count is None:
-            self._empty_count = torch.empty(0, dtype=torch.int64, device=self.device)
-        return self._empty_count
+        return native()
+
+    def _tick(self, key: str, t0: float) -> float:
+        """Producer timing (PA_PROD_TIMING=1, callers test ``_prod_timing``):
+        add the time since ``t0`` to ``_pt[key]`` unless the warm-up skip is
+        still running; -> now, the next stage's ``t0``."""
+        now = time.perf_counter()
+        if self._prod_timing_live:
+            self._pt[key] = self._pt.get(key, 0.0) + (now - t0)
+        return now
 
     @staticmethod
     def _materialize_group(group: "_GroupCtx") -> "_GroupCtx":
@@ -531,14 +581,12 @@ class EmbeddingEngine:
             # sorted keys is a range partition -> binary searches) + one
             # packed scatter — replaces the ~10-dispatch torch chain below
             # (measured 0.51 ms/batch of producer issue time)
-            from persia_amd.ops import native as _native
-
-            send, idx = _native().a2a_route(
+            return self._C.a2a_route(
                 uniq,
-                u_count if u_count is not None else self._empty_i64(),
+                u_count if u_count is not None
+                else self.stores[plan.dim].no_count,
                 world, cap, self._a2a_overflow,
             )
-            return send, idx
         n = uniq.numel()
         ar = plan.a2a_ar[:n]
         owner = _owner_of_keys(uniq, world)
@@ -568,25 +616,21 @@ class EmbeddingEngine:
         wire dtype -> even a2a back.  Returns (rows_full [world*cap+1, dim]
         with a zero dummy tail row, idx).  Fills group.a2a_* for backward."""
         world, cap = self._a2a_setup(plan)
-        if self._prod_timing:
-            _tr = time.perf_counter()
+        timing = self._prod_timing
+        if timing:
+            t = time.perf_counter()
         send_keys, idx = self._a2a_route(plan, group.uniq_keys, group.u_count)
         comm = self.dist
         if world > 1:
             recv_keys = comm.all_to_all_even(send_keys[: world * cap])
         else:
             recv_keys = send_keys[: world * cap].clone()
-        if self._prod_timing and getattr(self, "_prod_timing_live", True):
-            self._pt["route"] = self._pt.get("route", 0.0) + (
-                time.perf_counter() - _tr
-            )
-            _tr = time.perf_counter()
+        if timing:
+            t = self._tick("route", t)
         store = self.stores[group.dim]
         rows_local = store.lookup_wire(recv_keys, train, self.wire_dtype)
-        if self._prod_timing and getattr(self, "_prod_timing_live", True):
-            self._pt["lkw"] = self._pt.get("lkw", 0.0) + (
-                time.perf_counter() - _tr
-            )
+        if timing:
+            self._tick("lkw", t)
         rows_full = torch.empty(
             world * cap + 1, group.dim, dtype=rows_local.dtype,
             device=self.device,
@@ -604,9 +648,7 @@ class EmbeddingEngine:
             # sort overlaps the dense step on the pipeline stream (the fused
             # a2a_route freed the producer budget this costs);
             # _a2a_backward_native falls back lazily if absent (infer skips)
-            from persia_amd.ops import native as _native
-
-            group.a2a_owner_dedup = tuple(_native().dedup_padded(recv_keys))
+            group.a2a_owner_dedup = tuple(self._C.dedup_padded(recv_keys))
         return rows_full, idx
 
     def check_a2a_overflow(self) -> int:
@@ -620,11 +662,10 @@ class EmbeddingEngine:
     @_roctx_range("persia:process_batch")
     def process_batch(self, batch: PersiaBatch, train: Optional[bool] = None) -> PersiaTrainingBatch:
         if self._prod_timing:
-            if self._pt["skip"] > 0:
+            # timers skip the first batches (see _pt in __init__)
+            self._prod_timing_live = self._pt["skip"] <= 0
+            if not self._prod_timing_live:
                 self._pt["skip"] -= 1
-                self._prod_timing_live = False
-            else:
-                self._prod_timing_live = True
             _tb0 = time.perf_counter()
         self._batch_counter += 1
         sample = (
@@ -647,7 +688,6 @@ class EmbeddingEngine:
         out.batch_id = batch.batch_id
         out._engine = self
 
-        dev = self.device
         for i, x in enumerate(batch.non_id_type_features):
             out.non_id_type_tensors.append(
                 self._upload_aux(batch, ("nid", i), x.data)
@@ -655,14 +695,8 @@ class EmbeddingEngine:
         for i, x in enumerate(batch.labels):
             out.label_tensors.append(self._upload_aux(batch, ("lab", i), x.data))
 
-        feats_by_dim: Dict[int, List] = {}
-        for feat in batch.id_type_features:
-            cfg = self.schema.get_slot(feat.name)
-            feats_by_dim.setdefault(cfg.dim, []).append(feat)
-
-        for dim, feats in feats_by_dim.items():
-            group = self._process_group(dim, feats, out, train, src_batch=batch)
-            out._groups.append(group)
+        for dim, feats in self._feats_by_dim(batch).items():
+            out._groups.append(self._process_group(dim, feats, out, train, batch))
         # keep payloads in the original id_type_features order (applied
         # lazily when .payloads is first materialized)
         out._order = {f.name: i for i, f in enumerate(batch.id_type_features)}
@@ -670,7 +704,7 @@ class EmbeddingEngine:
         if sample:
             self._record_lookup_metrics(batch, out, _ms_t0, _ms_ev0)
         if self._prod_timing and self._prod_timing_live:
-            self._pt["batch"] += time.perf_counter() - _tb0
+            self._tick("batch", _tb0)
             self._pt["n"] += 1
         return out
 
@@ -735,10 +769,10 @@ class EmbeddingEngine:
                     g.uniq_keys.numel() / max(1, nnz)
                 )
             skip_pin = None
-            store = next(iter(self.stores.values()))
-            if hasattr(store, "_skipped"):
+            skipped = next(iter(self.stores.values())).skip_counters()
+            if skipped is not None:
                 skip_pin = torch.empty(2, dtype=torch.int32, pin_memory=True)
-                skip_pin.copy_(store._skipped, non_blocking=True)
+                skip_pin.copy_(skipped, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
             self._pending_metric = (ev0, ev1, ucnt_pin, skip_pin, nnz, done)
@@ -770,25 +804,25 @@ class EmbeddingEngine:
         for kind, items in (("nid", batch.non_id_type_features),
                             ("lab", batch.labels)):
             for i, x in enumerate(items):
-                if (kind, i) in pc:
-                    continue
-                src = torch.from_numpy(np.ascontiguousarray(x.data))
-                t = torch.empty_like(src, pin_memory=True)
-                t.copy_(src)
-                pc[(kind, i)] = t
-        feats_by_dim: Dict[int, List] = {}
+                if (kind, i) not in pc:
+                    pc[(kind, i)] = self._pin_array(x.data)
+        for dim, feats in self._feats_by_dim(batch).items():
+            if dim not in pc and self._all_single_sum(feats):
+                pc[dim] = self._pin_values(feats)
+
+    def _feats_by_dim(self, batch: PersiaBatch) -> Dict[int, List]:
+        """A batch's id features by dim-group (one store + one a2a each)."""
+        by_dim: Dict[int, List] = {}
         for feat in batch.id_type_features:
-            cfg = self.schema.get_slot(feat.name)
-            feats_by_dim.setdefault(cfg.dim, []).append(feat)
-        for dim, feats in feats_by_dim.items():
-            if dim in pc or not all(
-                getattr(f, "is_single", False) for f in feats
-            ):
-                continue
-            values_np = np.concatenate([f.values for f in feats])
-            pin = torch.empty(len(values_np), dtype=torch.int64, pin_memory=True)
-            pin.numpy()[:] = values_np.view(np.int64)
-            pc[dim] = pin
+            by_dim.setdefault(self.schema.get_slot(feat.name).dim, []).append(feat)
+        return by_dim
+
+    @staticmethod
+    def _pin_array(arr: np.ndarray) -> torch.Tensor:
+        src = torch.from_numpy(np.ascontiguousarray(arr))
+        t = torch.empty_like(src, pin_memory=True)
+        t.copy_(src)
+        return t
 
     def _upload_aux(self, batch, cache_key, arr: np.ndarray) -> torch.Tensor:
         """Dense-feature/label upload: pageable H2D stalls the pipeline
@@ -801,74 +835,73 @@ class EmbeddingEngine:
             pc = batch._pinned_cache = {}
         t = pc.get(cache_key)
         if t is None:
-            src = torch.from_numpy(np.ascontiguousarray(arr))
-            t = torch.empty_like(src, pin_memory=True)
-            t.copy_(src)
-            pc[cache_key] = t
+            t = pc[cache_key] = self._pin_array(arr)
         return t.to(self.device, non_blocking=True)
 
-    def _upload_values(self, dim: int, values_np: np.ndarray) -> torch.Tensor:
-        """Pinned-ring H2D: copy the host ids into a pinned slot and issue an
-        async copy (pageable uploads stall the lookup thread ~0.2ms/batch)."""
-        n = len(values_np)
-        ring = self._pin_rings.setdefault(dim, [])
-        if not ring or ring[0][0].numel() < n:
-            ring.clear()
-            for _ in range(12):  # > staleness window
-                ring.append(
-                    (torch.empty(n, dtype=torch.int64, pin_memory=True),
-                     torch.cuda.Event())
-                )
-            self._pin_idx[dim] = 0
-        idx = self._pin_idx[dim]
-        self._pin_idx[dim] = (idx + 1) % len(ring)
-        buf, ev = ring[idx]
-        ev.synchronize()  # previous H2D from this slot must be done
-        buf.numpy()[:n] = values_np.view(np.int64)
-        vals_t = buf[:n].to(self.device, non_blocking=True)
-        ev.record()
-        return vals_t
+    def _pin_values(self, feats) -> torch.Tensor:
+        """A group's raw ids, concatenated into a fresh pinned i64 buffer."""
+        values_np = np.concatenate([f.values for f in feats])
+        pin = torch.empty(len(values_np), dtype=torch.int64, pin_memory=True)
+        pin.numpy()[:] = values_np.view(np.int64)
+        return pin
 
-    def _process_group_fast(self, dim: int, feats, out: PersiaTrainingBatch,
-                            train: bool, src_batch=None) -> _GroupCtx:
-        """All-single-ID sum-slot fast path (flagship DLRM shape): one H2D
-        upload, ~15 kernel launches, static device-side plan."""
-        from persia_amd.ops import native as _native
+    def _upload_group(self, dim: int, feats, batch) -> torch.Tensor:
+        """One async H2D of a fast-path group's raw ids through the batch's
+        pinned staging (allocated once per PersiaBatch, like a loader-side
+        pinned pool: repeat visits are a pure async copy; pageable uploads
+        stall the lookup thread ~0.2ms/batch)."""
+        pcache = getattr(batch, "_pinned_cache", None)
+        if pcache is None:
+            pcache = batch._pinned_cache = {}
+        pin = pcache.get(dim)
+        if pin is None:
+            pin = pcache[dim] = self._pin_values(feats)
+        return pin.to(self.device, non_blocking=True)
 
-        if self._prod_timing:
-            _t0 = time.perf_counter()
-        C = _native()
-        dev = self.device
-        B = len(feats[0].values)
-        names = tuple(f.name for f in feats)
+    def _all_single_sum(self, feats) -> bool:
+        """The fast-path shape (flagship DLRM): every feature carries one id
+        per sample and is a sum slot without hashstack."""
+        get_slot = self.schema.get_slot
+        for f in feats:
+            if not getattr(f, "is_single", False):
+                return False
+            cfg = get_slot(f.name)
+            if not cfg.embedding_summation or cfg.hash_stack_rounds != 0:
+                return False
+        return True
+
+    def _padded_a2a(self, store) -> bool:
+        """Rows travel over the capacity-padded even a2a (not the two-phase
+        counts exchange): distributed, or PA_FORCE_DIST at one rank, with
+        PA_FUSED_DIST on and no spill tier."""
+        return (
+            (self.dist.distributed or self._force_dist)
+            and self._fused_dist
+            and store.spill is None
+        )
+
+    def _plan(self, dim: int, names: Tuple[str, ...], B: int) -> _GroupPlan:
         plan = self._plans.get((dim, names, B))
         if plan is None:
-            prefixes_np = np.array(
-                [self.schema.get_slot(n).index_prefix for n in names], dtype=np.uint64
+            cfgs = [self.schema.get_slot(n) for n in names]
+            plan = self._plans[(dim, names, B)] = _GroupPlan(
+                dim, cfgs, B, self.device
             )
-            plan = _GroupPlan(dim, names, prefixes_np, B, dev)
-            self._plans[(dim, names, B)] = plan
-        # per-batch pinned staging (allocated once per PersiaBatch, like a
-        # loader-side pinned pool): repeat visits are a pure async H2D
-        def _upload():
-            pcache = (
-                getattr(src_batch, "_pinned_cache", None)
-                if src_batch is not None else None
-            )
-            if pcache is not None and dim in pcache:
-                return pcache[dim].to(dev, non_blocking=True)
-            values_np = np.concatenate([f.values for f in feats])
-            if src_batch is not None:
-                if pcache is None:
-                    pcache = src_batch._pinned_cache = {}
-                pin = torch.empty(len(values_np), dtype=torch.int64, pin_memory=True)
-                pin.numpy()[:] = values_np.view(np.int64)
-                pcache[dim] = pin
-                return pin.to(dev, non_blocking=True)
-            return self._upload_values(dim, values_np)
+        return plan
 
-        spacing = self.schema.feature_spacing
-        spacing_arg = spacing if spacing < (1 << 63) else -1
+    def _process_group_fast(self, dim: int, feats, out: PersiaTrainingBatch,
+                            train: bool, batch: PersiaBatch) -> _GroupCtx:
+        """All-single-ID sum-slot fast path on a static device-side plan:
+        upload -> keys -> dedup -> rows -> sums -> group, ~15 kernel launches.
+        Three variants replace stages of that chain: one native call for all
+        of it, the front half on the spill probe stream, rows over the padded
+        a2a."""
+        timing = self._prod_timing
+        if timing:
+            t0 = time.perf_counter()
+        C = self._C
+        B = len(feats[0].values)
+        plan = self._plan(dim, tuple(f.name for f in feats), B)
         slot_ctxs = [
             _SlotCtx(
                 name=f.name, cfg=self.schema.get_slot(f.name),
@@ -878,146 +911,119 @@ class EmbeddingEngine:
             for i, f in enumerate(feats)
         ]
         store = self.stores[dim]
-        dist_fast = (
-            (self.dist.distributed or self._force_dist)
-            and self._fused_dist
-            and store.spill is None
-        )
-        # spill-tier front half on a dedicated probe stream: the miss-mask
-        # readback in spill_restore then waits only for this batch's tiny
-        # probe work, not the lookup stream's multi-batch backlog (the
-        # dcn-spill ~1.9 ms/batch producer stall — round-1 profiles finding)
-        spill_front = (
-            store.spill is not None and not self.dist.distributed and train
-        )
-        if not self.dist.distributed and store.spill is None and not self._force_dist:
-            # whole lookup in ONE native call (C++ drives sign prep, dedup,
+        dist = self.dist.distributed
+        one_call = not (dist or self._force_dist or store.spill is not None)
+        padded = not one_call and self._padded_a2a(store)
+        if one_call:
+            # upload..sums in ONE native call (C++ drives sign prep, dedup,
             # probe/insert, gather and the fused segment-sum)
-            if self._prod_timing and self._prod_timing_live:
-                self._pt["prep"] += time.perf_counter() - _t0
-            if self._prod_timing:
-                _t1 = time.perf_counter()
-            lo, hi = self.hyper.emb_initialization
-            vals_t = _upload()
-            sums, uniq_keys, inverse, perm, ustarts, u_count = C.lookup_local(
-                vals_t, plan.slot_starts, plan.prefixes, spacing_arg,
-                plan.cat_offsets, plan.empty_scale,
-                store.keys, store.ticks, store.arena, dim,
-                1 if train else 0, store.next_tick(), float(lo), float(hi),
-                float(self.hyper.admit_probability),
-                float(self.optimizer.state_init(dim)), store.opt_space,
+            if timing:
+                t0 = self._tick("prep", t0)
+            sums, uniq, inverse, perm, ustarts, u_count = store.lookup_local(
+                self._upload_group(dim, feats, batch), plan.slot_starts,
+                plan.prefixes, self._spacing_arg, plan.cat_offsets,
+                plan.empty_scale, train,
             )
-            group = _GroupCtx(
-                dim=dim, uniq_keys=uniq_keys, inverse=inverse, perm=perm,
-                ustarts=ustarts, u_count=u_count, slots=slot_ctxs,
-                cat_offsets=plan.cat_offsets, seg_id=plan.seg_id,
-                n_sum_slots=plan.S,
-            )
-            group.sum_base = sums
-            # defer SlotPayload construction (consumers on the fused path read
-            # group.sum_base directly; ~2*n_slots python objects per batch)
-            out._lazy_sum_groups.append((group, [sc.name for sc in slot_ctxs], B))
-            if self._prod_timing:
-                self._pt["native"] += time.perf_counter() - _t1
-            return group
         else:
-            if spill_front:
-                ps = store.probe_stream
-                cur = torch.cuda.current_stream()
-                with torch.cuda.stream(ps):
-                    vals_t = _upload()
-                    keys_t = C.sign_prep(
-                        vals_t, plan.slot_starts, plan.prefixes, spacing_arg
-                    )
-                    uniq_keys, inverse, perm, ustarts, u_count = C.dedup_padded(
-                        keys_t
-                    )
-                    store.spill_restore(uniq_keys, u_count)
-                cur.wait_stream(ps)
-                for t in (vals_t, uniq_keys, inverse, perm, ustarts, u_count):
-                    t.record_stream(cur)
-            else:
-                vals_t = _upload()
+            # spill tier (single GPU, training): upload..dedup plus the
+            # restore of spilled rows run on a dedicated probe stream, so the
+            # miss-mask readback in spill_restore waits only for this batch's
+            # tiny probe work, not the lookup stream's multi-batch backlog
+            # (the dcn-spill ~1.9 ms/batch producer stall)
+            ps = cur = None
+            if store.spill is not None and not dist and train:
+                ps, cur = store.probe_stream, torch.cuda.current_stream()
+            with torch.cuda.stream(ps) if ps is not None else _NO_STREAM:
+                vals_t = self._upload_group(dim, feats, batch)
                 keys_t = C.sign_prep(
-                    vals_t, plan.slot_starts, plan.prefixes, spacing_arg
+                    vals_t, plan.slot_starts, plan.prefixes, self._spacing_arg
                 )
-                if dist_fast or not self.dist.distributed:
-                    # sync-free padded dedup: both the fused distributed
-                    # exchange and the single-GPU spill path read the unique
-                    # count on-device
-                    uniq_keys, inverse, perm, ustarts, u_count = C.dedup_padded(
-                        keys_t
-                    )
+                if padded or not dist:
+                    # sync-free padded dedup: the fused distributed exchange
+                    # and the single-GPU store read the unique count on-device
+                    uniq, inverse, perm, ustarts, u_count = C.dedup_padded(keys_t)
                 else:
-                    uniq_keys, inverse, perm, ustarts = _dedup(keys_t)
+                    uniq, inverse, perm, ustarts = _dedup(keys_t)
                     u_count = None
-            group = _GroupCtx(
-                dim=dim, uniq_keys=uniq_keys, inverse=inverse, perm=perm,
-                ustarts=ustarts, u_count=u_count, slots=slot_ctxs,
-                cat_offsets=plan.cat_offsets, seg_id=plan.seg_id,
-                n_sum_slots=plan.S,
+                if ps is not None:
+                    store.spill_restore(uniq, u_count)
+            if ps is not None:
+                cur.wait_stream(ps)
+                for x in (vals_t, uniq, inverse, perm, ustarts, u_count):
+                    x.record_stream(cur)
+        group = _GroupCtx(
+            dim=dim, uniq_keys=uniq, inverse=inverse, perm=perm,
+            ustarts=ustarts, u_count=u_count, slots=slot_ctxs,
+            cat_offsets=plan.cat_offsets, seg_id=plan.seg_id,
+            n_sum_slots=plan.S,
+        )
+        if padded:
+            # rows over the capacity-padded even a2a (no host count syncs
+            # anywhere); the unpack gather is composed into `inverse` so
+            # segment_sum reads the recv buffer directly — no [nnz, dim] rows
+            if timing:
+                t = self._tick("dedup", t0)
+            rows_full, idx = self._a2a_exchange_fwd(plan, group, train)
+            if timing:
+                t = self._tick("exch", t)
+            sums = C.segment_sum(
+                rows_full, idx.gather(0, inverse), plan.cat_offsets,
+                plan.empty_scale,
             )
-            if dist_fast:
-                # capacity-padded even a2a (no host count syncs anywhere);
-                # compose the unpack gather into `inverse` so segment_sum
-                # reads the recv buffer directly — no [nnz, dim] row gather
-                if self._prod_timing and getattr(self, "_prod_timing_live", True):
-                    self._pt["dedup"] = self._pt.get("dedup", 0.0) + (
-                        time.perf_counter() - _t0
-                    )
-                    _tx = time.perf_counter()
-                rows_full, idx = self._a2a_exchange_fwd(plan, group, train)
-                if self._prod_timing and getattr(self, "_prod_timing_live", True):
-                    self._pt["exch"] = self._pt.get("exch", 0.0) + (
-                        time.perf_counter() - _tx
-                    )
-                    _tx = time.perf_counter()
-                inverse2 = idx.gather(0, inverse)
-                sums = C.segment_sum(
-                    rows_full, inverse2, plan.cat_offsets, plan.empty_scale
-                )
-                if self._prod_timing and getattr(self, "_prod_timing_live", True):
-                    self._pt["sum"] = self._pt.get("sum", 0.0) + (
-                        time.perf_counter() - _tx
-                    )
-                group.sum_base = sums
-                out._lazy_sum_groups.append(
-                    (group, [sc.name for sc in slot_ctxs], B)
-                )
-                if self._prod_timing and self._prod_timing_live:
-                    self._pt["native"] += time.perf_counter() - _t0
-                return group
+            if timing:
+                self._tick("sum", t)
+        elif not one_call:
             rows = self._exchange_rows(group, train)
             sums = C.segment_sum(
                 rows.contiguous(), inverse, plan.cat_offsets, plan.empty_scale
             )
-            group.sum_base = sums
-        for i, sc in enumerate(slot_ctxs):
-            out._payloads.append(
-                SlotPayload(name=sc.name, cfg=sc.cfg, sum_tensor=sums[i * B : (i + 1) * B])
-            )
+        group.sum_base = sums
+        # SlotPayload construction is deferred: consumers on the fused path
+        # read group.sum_base directly (~2*n_slots python objects per batch)
+        out._lazy_sum_groups.append((group, [sc.name for sc in slot_ctxs], B))
+        if timing and (one_call or padded):
+            self._tick("native", t0)
         return group
 
     def _process_group(self, dim: int, feats, out: PersiaTrainingBatch, train: bool,
-                       src_batch=None) -> _GroupCtx:
-        dev = self.device
-        native = dev.type == "cuda"
-        if native:
-            from persia_amd.ops import native as _native
-
-            C = _native()
-            if all(getattr(f, "is_single", False) for f in feats) and all(
-                self.schema.get_slot(f.name).embedding_summation
-                and self.schema.get_slot(f.name).hash_stack_rounds == 0
-                for f in feats
-            ):
-                return self._process_group_fast(dim, feats, out, train, src_batch)
+                       batch: PersiaBatch) -> _GroupCtx:
+        native = self.device.type == "cuda"
+        fast_shape = self._all_single_sum(feats)
+        if native and fast_shape:
+            return self._process_group_fast(dim, feats, out, train, batch)
         # sum slots first so they occupy a contiguous prefix of the position
         # space (one fused segment-sum launch for the whole group)
         feats = sorted(
             feats, key=lambda f: 0 if self.schema.get_slot(f.name).embedding_summation else 1
         )
-        gpu_prep = native
+        keys_t, slot_ctxs = self._group_keys(feats, gpu_prep=native)
+        uniq_keys, inverse, perm, ustarts = _dedup(keys_t)
+        group = _GroupCtx(
+            dim=dim, uniq_keys=uniq_keys, inverse=inverse, perm=perm,
+            ustarts=ustarts, slots=slot_ctxs,
+        )
+        if not native and fast_shape and self._padded_a2a(self.stores[dim]):
+            # CPU mirror of the GPU fused distributed path: same capacity-padded
+            # even-a2a routing math, exact (unpadded) dedup — this is what the
+            # gloo multi-process tests exercise so the 8-GPU driver run's code
+            # path has CPU coverage
+            plan = self._plan(
+                dim, tuple(sc.name for sc in slot_ctxs), out.batch_size
+            )
+            rows_full, idx = self._a2a_exchange_fwd(plan, group, train)
+            rows = rows_full[idx]
+        else:
+            rows = self._exchange_rows(group, train)  # [U, dim]
+        self._sum_payloads(group, rows, out)
+        self._raw_payloads(group, rows, out)
+        return group
+
+    def _group_keys(self, feats, gpu_prep: bool):
+        """Generic path, stage 1: -> (mixed keys i64[nnz'] on the device in
+        slot order, one _SlotCtx per feature with its position slice and
+        per-sample offsets).  CPU: sign prep on the host; GPU: raw ids are
+        uploaded and hashstack expansion + prefix + mix run in one kernel."""
+        dev = self.device
         key_arrays = []
         offset_arrays = []
         slot_ctxs: List[_SlotCtx] = []
@@ -1029,7 +1035,6 @@ class EmbeddingEngine:
             cfg = self.schema.get_slot(feat.name)
             r = cfg.hash_stack_rounds
             if gpu_prep:
-                # raw ids; hashstack expansion + prefix + mix all on-GPU.
                 # expanded seg offsets are exactly offsets*r (every segment
                 # grows by the same factor)
                 keys = feat.values
@@ -1045,146 +1050,119 @@ class EmbeddingEngine:
             sizes_list.append(
                 cfg.hash_stack_config.embedding_size if r > 0 else 1
             )
-            sc = _SlotCtx(name=feat.name, cfg=cfg, pos_slice=(pos, pos + out_len),
-                          seg_offsets=None)
-            slot_ctxs.append(sc)
+            slot_ctxs.append(
+                _SlotCtx(name=feat.name, cfg=cfg, pos_slice=(pos, pos + out_len),
+                         seg_offsets=None)
+            )
             pos += out_len
 
         all_keys = np.concatenate(key_arrays) if key_arrays else np.empty(0, np.uint64)
         # single H2D upload of the whole group's values + all offsets
         keys_t = torch.from_numpy(all_keys.view(np.int64)).to(dev, non_blocking=False)
-        all_offs = np.concatenate(
-            [o for o in offset_arrays] or [np.zeros(1, np.int64)]
-        )
+        all_offs = np.concatenate(offset_arrays or [np.zeros(1, np.int64)])
         all_offs_t = torch.from_numpy(all_offs).to(dev)
         o0 = 0
         for sc, offs in zip(slot_ctxs, offset_arrays):
             sc.seg_offsets = all_offs_t[o0 : o0 + len(offs)]
             o0 += len(offs)
-        if gpu_prep:
-            out_starts = torch.tensor(
-                [sc.pos_slice[0] for sc in slot_ctxs] + [pos],
-                dtype=torch.int64, device=dev,
-            )
-            prefixes = torch.from_numpy(
-                np.array([sc.cfg.index_prefix for sc in slot_ctxs], dtype=np.uint64)
-                .view(np.int64)
-            ).to(dev)
-            spacing = self.schema.feature_spacing
-            spacing_arg = spacing if spacing < (1 << 63) else -1
-            from persia_amd.ops import native as _native2
-
-            if any(rounds_list):
-                in_starts = torch.from_numpy(
-                    np.concatenate([[0], np.cumsum(in_lens)]).astype(np.int64)
-                ).to(dev)
-                off_starts = torch.from_numpy(
-                    np.concatenate(
-                        [[0], np.cumsum([len(o) for o in offset_arrays])]
-                    ).astype(np.int64)
-                ).to(dev)
-                keys_t = _native2().sign_prep_stack(
-                    keys_t, in_starts, out_starts, prefixes,
-                    torch.tensor(rounds_list, dtype=torch.int32, device=dev),
-                    torch.tensor(sizes_list, dtype=torch.int64, device=dev),
-                    off_starts, all_offs_t, spacing_arg, pos,
-                )
-            else:
-                keys_t = _native2().sign_prep(
-                    keys_t, out_starts, prefixes, spacing_arg
-                )
-
-        uniq_keys, inverse, perm, ustarts = _dedup(keys_t)
-        group = _GroupCtx(
-            dim=dim, uniq_keys=uniq_keys, inverse=inverse, perm=perm,
-            ustarts=ustarts, slots=slot_ctxs,
+        if not gpu_prep:
+            return keys_t, slot_ctxs
+        out_starts = torch.tensor(
+            [sc.pos_slice[0] for sc in slot_ctxs] + [pos],
+            dtype=torch.int64, device=dev,
         )
-        # CPU mirror of the GPU fused distributed path: same capacity-padded
-        # even-a2a routing math, exact (unpadded) dedup — this is what the
-        # gloo multi-process tests exercise so the 8-GPU driver run's code
-        # path has CPU coverage
-        use_padded = (
-            not native
-            and (self.dist.distributed or self._force_dist)
-            and self._fused_dist
-            and self.stores[dim].spill is None
-            and all(getattr(f, "is_single", False) for f in feats)
-            and all(
-                sc.cfg.embedding_summation and sc.cfg.hash_stack_rounds == 0
-                for sc in slot_ctxs
-            )
+        prefixes = torch.from_numpy(
+            np.array([sc.cfg.index_prefix for sc in slot_ctxs], dtype=np.uint64)
+            .view(np.int64)
+        ).to(dev)
+        if not any(rounds_list):
+            return self._C.sign_prep(
+                keys_t, out_starts, prefixes, self._spacing_arg
+            ), slot_ctxs
+        in_starts = torch.from_numpy(
+            np.concatenate([[0], np.cumsum(in_lens)]).astype(np.int64)
+        ).to(dev)
+        off_starts = torch.from_numpy(
+            np.concatenate(
+                [[0], np.cumsum([len(o) for o in offset_arrays])]
+            ).astype(np.int64)
+        ).to(dev)
+        keys_t = self._C.sign_prep_stack(
+            keys_t, in_starts, out_starts, prefixes,
+            torch.tensor(rounds_list, dtype=torch.int32, device=dev),
+            torch.tensor(sizes_list, dtype=torch.int64, device=dev),
+            off_starts, all_offs_t, self._spacing_arg, pos,
         )
-        if use_padded:
-            B = out.batch_size
-            names = tuple(sc.name for sc in slot_ctxs)
-            plan = self._plans.get((dim, names, B))
-            if plan is None:
-                prefixes_np = np.array(
-                    [self.schema.get_slot(n).index_prefix for n in names],
-                    dtype=np.uint64,
-                )
-                plan = _GroupPlan(dim, names, prefixes_np, B, dev)
-                self._plans[(dim, names, B)] = plan
-            rows_full, idx = self._a2a_exchange_fwd(plan, group, train)
-            rows = rows_full[idx]
+        return keys_t, slot_ctxs
+
+    def _sum_payloads(self, group: _GroupCtx, rows: torch.Tensor,
+                      out: PersiaTrainingBatch) -> None:
+        """Generic path: fused postprocess of the group's sum slots (one
+        segment-sum over their contiguous position prefix) into
+        ``group.sum_base`` and one sum payload per slot."""
+        sum_slots = [sc for sc in group.slots if sc.cfg.embedding_summation]
+        if not sum_slots:
+            return
+        dev = self.device
+        base = 0
+        offs_parts, sqrt_parts = [], []
+        for sc in sum_slots:
+            s, _e = sc.pos_slice
+            sc.sum_seg_base = base
+            nseg = sc.seg_offsets.numel() - 1
+            offs_parts.append(sc.seg_offsets[:-1] + s)
+            sqrt_parts.append(
+                torch.full((nseg,), bool(sc.cfg.sqrt_scaling), dtype=torch.bool, device=dev)
+            )
+            base += nseg
+        sum_end = sum_slots[-1].pos_slice[1]
+        cat_offsets = torch.cat(
+            offs_parts + [torch.tensor([sum_end], dtype=torch.int64, device=dev)]
+        )
+        group.cat_offsets = cat_offsets
+        group.sqrt_mask = torch.cat(sqrt_parts)
+        seg_counts = cat_offsets[1:] - cat_offsets[:-1]
+        group.seg_lens = seg_counts.float()
+        seg_id = torch.full(
+            (group.inverse.numel(),), -1, dtype=torch.int64, device=dev
+        )
+        seg_id[:sum_end] = torch.repeat_interleave(
+            torch.arange(base, dtype=torch.int64, device=dev), seg_counts
+        )
+        group.seg_id = seg_id
+        fwd_scale = _sqrt_scale(group.sqrt_mask, group.seg_lens)
+        if dev.type == "cuda":
+            sums = self._C.segment_sum(
+                rows.contiguous(), group.inverse, cat_offsets, fwd_scale
+            )
         else:
-            rows = self._exchange_rows(group, train)  # [U, dim]
-
-        # ---- fused sum-slot postprocess
-        sum_slots = [sc for sc in slot_ctxs if sc.cfg.embedding_summation]
-        if sum_slots:
-            base = 0
-            offs_parts, sqrt_parts = [], []
-            for sc in sum_slots:
-                s, _e = sc.pos_slice
-                sc.sum_seg_base = base
-                nseg = sc.seg_offsets.numel() - 1
-                offs_parts.append(sc.seg_offsets[:-1] + s)
-                sqrt_parts.append(
-                    torch.full((nseg,), bool(sc.cfg.sqrt_scaling), dtype=torch.bool, device=dev)
+            sums = (
+                R.segment_sum_rows(
+                    rows, group.inverse[:sum_end], cat_offsets, False, torch.float32
                 )
-                base += nseg
-            sum_end = sum_slots[-1].pos_slice[1]
-            cat_offsets = torch.cat(
-                offs_parts + [torch.tensor([sum_end], dtype=torch.int64, device=dev)]
+                * fwd_scale.unsqueeze(1)
+            ).to(torch.float16)
+        group.sum_base = sums
+        group.n_sum_slots = len(sum_slots)
+        b0 = 0
+        for sc in sum_slots:
+            nseg = sc.seg_offsets.numel() - 1
+            out._payloads.append(
+                SlotPayload(name=sc.name, cfg=sc.cfg, sum_tensor=sums[b0 : b0 + nseg])
             )
-            group.cat_offsets = cat_offsets
-            group.sqrt_mask = torch.cat(sqrt_parts)
-            lens = (cat_offsets[1:] - cat_offsets[:-1]).float()
-            group.seg_lens = lens
-            n_sum_segs = base
-            seg_id = torch.full((inverse.numel(),), -1, dtype=torch.int64, device=dev)
-            seg_id[:sum_end] = torch.repeat_interleave(
-                torch.arange(n_sum_segs, dtype=torch.int64, device=dev),
-                (cat_offsets[1:] - cat_offsets[:-1]),
-            )
-            group.seg_id = seg_id
-            fwd_scale = torch.where(
-                group.sqrt_mask, lens.clamp(min=1.0).rsqrt(), torch.ones_like(lens)
-            )
-            if native:
-                sums = C.segment_sum(rows.contiguous(), inverse, cat_offsets, fwd_scale)
-            else:
-                sums = (
-                    R.segment_sum_rows(rows, inverse[:sum_end], cat_offsets, False, torch.float32)
-                    * fwd_scale.unsqueeze(1)
-                ).to(torch.float16)
-            group.sum_base = sums
-            group.n_sum_slots = len(sum_slots)
-            b0 = 0
-            for sc in sum_slots:
-                nseg = sc.seg_offsets.numel() - 1
-                p = SlotPayload(name=sc.name, cfg=sc.cfg, sum_tensor=sums[b0 : b0 + nseg])
-                out._payloads.append(p)
-                b0 += nseg
+            b0 += nseg
 
-        # ---- raw slots (torch path both backends: not in the flagship loop)
-        for sc in slot_ctxs:
+    def _raw_payloads(self, group: _GroupCtx, rows: torch.Tensor,
+                      out: PersiaTrainingBatch) -> None:
+        """Generic path: raw slots (torch on both backends: not in the
+        flagship loop) -> distinct rows + index tensors per slot."""
+        for sc in group.slots:
             if sc.cfg.embedding_summation:
                 continue
             s, e = sc.pos_slice
-            inv_slot = inverse[s:e]
-            slot_uniq, slot_inv = torch.unique(inv_slot, sorted=True, return_inverse=True)
+            slot_uniq, slot_inv = torch.unique(
+                group.inverse[s:e], sorted=True, return_inverse=True
+            )
             sc.slot_uniq_global = slot_uniq
             sc.slot_inverse = slot_inv
             scale = 1.0
@@ -1201,11 +1179,62 @@ class EmbeddingEngine:
                     raw_non_empty_index=non_empty, raw_sample_id_num=num,
                 )
             )
-        return group
 
     # --------------------------------------------------------- backward path
 
-    @_roctx_range("persia:update")
+    def _seg_scale(self, group: _GroupCtx, loss_scale: float,
+                   skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-segment gradient scale of a group's sum slots: 1/loss_scale,
+        times the sqrt-scaling factor, zeroed where ``skip`` (bool per
+        segment: a NaN slot's segments).  The empty tensor means all ones.
+        A ``skip`` caller builds the tensor anyway, so only the others pay
+        the ``any()`` readback that can spare it."""
+        mask = group.sqrt_mask
+        has_sqrt = mask is not None and (skip is not None or bool(mask.any()))
+        if skip is None and loss_scale == 1.0 and not has_sqrt:
+            return self._empty_scale
+        scale = torch.full(
+            (group.cat_offsets.numel() - 1,), 1.0 / loss_scale,
+            device=self.device,
+        )
+        if has_sqrt:
+            scale = scale * _sqrt_scale(mask, group.seg_lens)
+        if skip is not None:
+            scale = torch.where(skip, torch.zeros_like(scale), scale)
+        return scale
+
+    def _nan_slot(self, sc: _SlotCtx, g: torch.Tensor) -> bool:
+        """Host-side NaN filter of one slot's gradient (reference
+        mod.rs:731-746: skip the whole slot)."""
+        if not bool(torch.isnan(g).any()):
+            return False
+        self.nan_grad_batches += 1
+        _logger.warning(f"nan found in gradient update of {sc.name}, skipping")
+        return True
+
+    def _add_raw_grads(self, group: _GroupCtx, grads, loss_scale: float,
+                       buf: torch.Tensor) -> bool:
+        """Accumulate the raw slots' (U_slot, dim) gradients (the index_add_
+        de-dup output of ctx._on_backward) into the per-unique buffer;
+        -> whether any slot contributed."""
+        added = False
+        for sc in group.slots:
+            if sc.cfg.embedding_summation:
+                continue
+            g = grads.get(sc.name)
+            if g is None or self._nan_slot(sc, g):
+                continue
+            gf = g.float()
+            if loss_scale != 1.0:
+                gf = gf / loss_scale
+            rounds = sc.cfg.hash_stack_rounds
+            if sc.cfg.sqrt_scaling and rounds > 0:
+                gf = gf / float(np.sqrt(rounds))
+            buf.index_add_(0, sc.slot_uniq_global, gf)
+            added = True
+        return added
+
+    @_update_entry
     def apply_gradients(
         self,
         training_batch: PersiaTrainingBatch,
@@ -1215,105 +1244,63 @@ class EmbeddingEngine:
         """grads: slot name -> grad tensor ((B,dim) f16 for sum slots,
         (U_slot, dim) f32 for raw slots — the contract of ctx._on_backward,
         reference persia/ctx.py:926-1005) or None (skipped)."""
-        self._update_counter += 1
-        usample = (
-            self.metrics_enabled
-            and self._update_counter % self._metrics_every
-            == 1 % self._metrics_every
-        )
-        if usample:
-            _ut0 = time.perf_counter()
-        native = self.device.type == "cuda"
-        if native:
-            from persia_amd.ops import native as _native
+        self._apply_slot_grads(training_batch, grads, loss_scale)
 
-            C = _native()
+    def _apply_slot_grads(self, training_batch, grads, loss_scale) -> None:
+        native = self.device.type == "cuda"
+        B = training_batch.batch_size
         for group in training_batch._groups:
             self._materialize_group(group)  # generic path needs exact U
             U = group.uniq_keys.numel()
             buf = torch.zeros(U, group.dim, dtype=torch.float32, device=self.device)
+            sum_slots = [
+                sc for sc in group.slots
+                if sc.cfg.embedding_summation and grads.get(sc.name) is not None
+            ]
+            # no sum-slot grads at all: no fused launch, so a fully skipped
+            # group never applies a zero-gradient optimizer step (reference
+            # skip-the-slot semantics, mod.rs:731-746)
             any_grad = False
-            sum_slots = [sc for sc in group.slots if sc.cfg.embedding_summation]
-            # all-None slot grads: skip the fused launch entirely so a fully
-            # skipped group never applies a zero-gradient optimizer step
-            # (reference skip-the-slot semantics, mod.rs:731-746)
-            if native and sum_slots and not any(
-                grads.get(sc.name) is not None for sc in sum_slots
-            ):
-                sum_slots = []
             if native and sum_slots:
                 # fused ordered scatter over ALL sum slots in one launch.
-                # Per-slot NaN skip (reference mod.rs:731-746) without a host
-                # sync: zero the slot's per-segment scale via a device flag
-                # and sanitize the grads (NaN*0 would still be NaN).
+                # Per-slot NaN skip without a host sync: zero the slot's
+                # per-segment scale via a device flag and sanitize the grads
+                # (NaN*0 would still be NaN); a None slot is a skipped one.
                 g_parts, flag_parts = [], []
-                B = training_batch.batch_size
-                for sc in sum_slots:
+                for sc in group.slots:
+                    if not sc.cfg.embedding_summation:
+                        continue
                     g = grads.get(sc.name)
                     if g is None:
                         g = torch.zeros(B, group.dim, dtype=torch.float16, device=self.device)
                         flag = torch.ones((), dtype=torch.bool, device=self.device)
                     else:
-                        any_grad = True
                         flag = torch.isnan(g).any()
                     g_parts.append(g.to(torch.float16))
-                    flag_parts.append(flag.expand(sc.seg_offsets.numel() - 1))
-                grads_cat = torch.nan_to_num(torch.cat(g_parts, dim=0))
-                skip = torch.cat(flag_parts)
-                lens = group.seg_lens
-                scale = torch.where(
-                    group.sqrt_mask, lens.clamp(min=1.0).rsqrt(), torch.ones_like(lens)
-                )
-                if loss_scale != 1.0:
-                    scale = scale / loss_scale
-                scale = torch.where(skip, torch.zeros_like(scale), scale)
-                C.grad_scatter(
-                    grads_cat.contiguous(), group.perm, group.ustarts,
-                    group.seg_id, scale.contiguous(), buf, 1,
+                    flag_parts.append(flag.expand(B))
+                scale = self._seg_scale(group, loss_scale, skip=torch.cat(flag_parts))
+                self._C.grad_scatter(
+                    torch.nan_to_num(torch.cat(g_parts, dim=0)).contiguous(),
+                    group.perm, group.ustarts, group.seg_id, scale.contiguous(),
+                    buf, 1,
                 )
                 any_grad = True  # kernels launched regardless (no host sync)
-            for sc in group.slots:
-                g = grads.get(sc.name)
-                if g is None:
-                    continue
-                if native and sc.cfg.embedding_summation:
-                    continue  # handled by the fused scatter above
-                # NaN filter (reference mod.rs:731-746: skip the whole slot)
-                if bool(torch.isnan(g).any()):
-                    self.nan_grad_batches += 1
-                    _logger.warning(f"nan found in gradient update of {sc.name}, skipping")
-                    continue
-                any_grad = True
-                s, e = sc.pos_slice
-                inv_slot = group.inverse[s:e]
-                if sc.cfg.embedding_summation:
-                    contrib = R.segment_grad_scatter(
-                        g,
-                        inv_slot,
-                        sc.seg_offsets,
-                        U,
-                        scale_factor=loss_scale,
-                        sqrt_scaling=sc.cfg.sqrt_scaling,
+            elif not native:
+                for sc in sum_slots:
+                    g = grads[sc.name]
+                    if self._nan_slot(sc, g):
+                        continue
+                    any_grad = True
+                    s, e = sc.pos_slice
+                    buf += R.segment_grad_scatter(
+                        g, group.inverse[s:e], sc.seg_offsets, U,
+                        scale_factor=loss_scale, sqrt_scaling=sc.cfg.sqrt_scaling,
                     )
-                    buf += contrib
-                else:
-                    gf = g.float()
-                    if loss_scale != 1.0:
-                        gf = gf / loss_scale
-                    rounds = sc.cfg.hash_stack_rounds
-                    if sc.cfg.sqrt_scaling and rounds > 0:
-                        gf = gf / float(np.sqrt(rounds))
-                    buf.index_add_(0, sc.slot_uniq_global, gf)
-            if not any_grad:
-                continue
-            self._route_and_update(group, buf)
-        if usample:
-            self.metrics.update_gradient_time_cost_sec.set(
-                time.perf_counter() - _ut0
-            )
+            if self._add_raw_grads(group, grads, loss_scale, buf) or any_grad:
+                self._route_and_update(group, buf)
 
     def _a2a_backward_native(self, group: _GroupCtx, gbase: torch.Tensor,
-                             seg_scale: torch.Tensor, store, C) -> None:
+                             seg_scale: torch.Tensor, store) -> None:
         """GPU fused distributed backward: per-uniq ordered grad reduction
         written directly into the padded a2a send layout (f16 wire), even
         all-to-all on the grad communicator, then owner-side fused
@@ -1323,10 +1310,10 @@ class EmbeddingEngine:
         send_g = torch.empty(
             world * cap + 1, group.dim, dtype=torch.float16, device=self.device
         )
-        uc = group.u_count if group.u_count is not None else self._empty_i64()
-        C.grad_scatter_idx(
+        self._C.grad_scatter_idx(
             gbase.contiguous(), group.perm, group.ustarts, group.seg_id,
-            seg_scale, group.a2a_idx, send_g, uc,
+            seg_scale, group.a2a_idx, send_g,
+            group.u_count if group.u_count is not None else store.no_count,
         )
         if world > 1:
             recv_g = self.dist_grad.all_to_all_even(send_g[: world * cap])
@@ -1335,29 +1322,44 @@ class EmbeddingEngine:
         # positions whose recv key is 0 (bucket padding) were never written:
         # scatter_update skips them on the key, before reading the grads
         if group.a2a_owner_dedup is None:
-            group.a2a_owner_dedup = tuple(C.dedup_padded(group.a2a_recv_keys))
+            group.a2a_owner_dedup = tuple(
+                self._C.dedup_padded(group.a2a_recv_keys)
+            )
         ou, _oinv, operm, oustarts, ou_count = group.a2a_owner_dedup
-        powers = store._adam_step_powers()
-        b1p, b2p = powers if powers else (0.0, 0.0)
-        C.scatter_update(
-            store.keys, store.ticks, store.arena, ou, recv_g, operm,
-            oustarts, plan.owner_seg_id, self._empty_f32(), group.dim,
-            store._opt_code, store._opt_params(), float(b1p), float(b2p),
-            float(self.hyper.weight_bound), store._skipped, ou_count,
+        store.scatter_update(
+            ou, recv_g, operm, oustarts, plan.owner_seg_id, ou_count
         )
         if self.incremental is not None:
             # owner-side recording: this rank's shard's touched signs
             self.incremental.record_keys(ou, ou_count)
 
+    def _store_update(self, store, keys: torch.Tensor, grads: torch.Tensor) -> None:
+        """One optimizer application per key on this rank's shard."""
+        self.skipped_grad_signs += store.update_gradients(keys, grads)
+        if self.incremental is not None:
+            self.incremental.record_keys(keys)
+
+    def _owner_merge_update(self, store, keys_recv: torch.Tensor,
+                            grads_recv: torch.Tensor) -> None:
+        """Owner side of a gradient exchange: merge duplicate keys across
+        source ranks into ONE optimizer application per sign (the reference
+        applies each rank's RPC sequentially under a per-sign lock — summing
+        first is the synchronous-equivalent, deterministic, and race-free on
+        GPU)."""
+        uniq_f, inv = torch.unique(keys_recv ^ _FLIP, sorted=True, return_inverse=True)
+        merged = torch.zeros(
+            uniq_f.numel(), store.dim, dtype=torch.float32, device=self.device
+        )
+        merged.index_add_(0, inv, grads_recv.float())
+        self._store_update(store, uniq_f ^ _FLIP, merged)
+
     def _route_and_update_padded(self, group: _GroupCtx, buf: torch.Tensor) -> None:
         """CPU mirror of the padded backward (the gloo-tested twin of
         _a2a_backward_native): pack per-uniq grads into the fixed bucket
-        layout, even a2a, owner-side merge, ONE optimizer application per
-        sign (sum-first, deterministic — same semantics as
+        layout, even a2a, owner-side merge (same semantics as
         _route_and_update)."""
         plan = group.a2a_plan
         world, cap = plan.a2a_world, plan.a2a_cap
-        store = self.stores[group.dim]
         send_g = torch.zeros(
             world * cap + 1, group.dim, dtype=self.wire_dtype,
             device=self.device,
@@ -1373,27 +1375,15 @@ class EmbeddingEngine:
             recv_g = send_g[: world * cap]
         rk = group.a2a_recv_keys
         m = rk != 0
-        if not bool(m.any()):
-            return
-        uniq_f, inv = torch.unique(rk[m] ^ _FLIP, sorted=True, return_inverse=True)
-        merged = torch.zeros(
-            uniq_f.numel(), group.dim, dtype=torch.float32, device=self.device
-        )
-        merged.index_add_(0, inv, recv_g[m].float())
-        uk = uniq_f ^ _FLIP
-        self.skipped_grad_signs += store.update_gradients(uk, merged)
-        if self.incremental is not None:
-            self.incremental.record_keys(uk)
+        if bool(m.any()):
+            self._owner_merge_update(self.stores[group.dim], rk[m], recv_g[m])
 
     def _route_and_update(self, group: _GroupCtx, buf: torch.Tensor) -> None:
         store = self.stores[group.dim]
         if group.a2a_idx is not None:
             return self._route_and_update_padded(group, buf)
         if not self.dist.distributed:
-            self.skipped_grad_signs += store.update_gradients(group.uniq_keys, buf)
-            if self.incremental is not None:
-                self.incremental.record_keys(group.uniq_keys)
-            return
+            return self._store_update(store, group.uniq_keys, buf)
         comm = self.dist_grad  # main-thread communicator (see __init__)
         send_counts, recv_counts = group.send_counts, group.recv_counts
         if send_counts is None:
@@ -1404,21 +1394,9 @@ class EmbeddingEngine:
         grads_recv = comm.all_to_all(
             buf.to(self.wire_dtype), send_counts, recv_counts
         )
-        # merge duplicate keys across source ranks: pre-aggregate into one
-        # optimizer application per sign (the reference applies each rank's
-        # RPC sequentially under a per-sign lock — summing first is the
-        # synchronous-equivalent, deterministic, and race-free on GPU)
-        uniq_f, inv = torch.unique(keys_recv ^ _FLIP, sorted=True, return_inverse=True)
-        merged = torch.zeros(
-            uniq_f.numel(), group.dim, dtype=torch.float32, device=self.device
-        )
-        merged.index_add_(0, inv, grads_recv.float())
-        uk = uniq_f ^ _FLIP
-        self.skipped_grad_signs += store.update_gradients(uk, merged)
-        if self.incremental is not None:
-            self.incremental.record_keys(uk)
+        self._owner_merge_update(store, keys_recv, grads_recv)
 
-    @_roctx_range("persia:update")
+    @_update_entry
     def apply_gradients_base(
         self,
         training_batch: PersiaTrainingBatch,
@@ -1428,151 +1406,79 @@ class EmbeddingEngine:
     ) -> None:
         """Backward fast path: sum-slot gradients are read directly from
         ``group.sum_base.grad`` (the per-group base tensor that
-        ``prepare_features`` marked requires_grad), so there is no per-slot
-        cat/NaN-reduce cascade — one ordered scatter per group.
+        ``prepare_features`` marked requires_grad) or ``sum_base_grads[i]``,
+        so there is no per-slot cat/NaN-reduce cascade — one ordered scatter
+        per group.
 
         ``raw_grads``: slot name -> (U_slot, dim) f32 for raw slots (the
         index_add_ de-dup output of ctx._on_backward)."""
-        native = self.device.type == "cuda"
-        self._update_counter += 1
-        usample = (
-            self.metrics_enabled
-            and self._update_counter % self._metrics_every
-            == 1 % self._metrics_every
-        )
-        if usample:
-            _ut0 = time.perf_counter()
-        if not native:
-            # CPU: slice the base into the generic per-slot dict
+        groups = training_batch._groups
+        if sum_base_grads is None:
+            sum_base_grads = [
+                g.sum_base.grad if g.sum_base is not None else None
+                for g in groups
+            ]
+        if self.device.type != "cuda":
+            # CPU: slice each base into the per-slot dict contract
             grads: Dict[str, Optional[torch.Tensor]] = dict(raw_grads or {})
-            for group in training_batch._groups:
-                gbase = (
-                    group.sum_base.grad if group.sum_base is not None else None
-                )
+            B = training_batch.batch_size
+            for group, gbase in zip(groups, sum_base_grads):
                 b0 = 0
                 for sc in group.slots:
-                    if not sc.cfg.embedding_summation:
-                        continue
-                    nseg = training_batch.batch_size
-                    grads[sc.name] = (
-                        gbase[b0 : b0 + nseg] if gbase is not None else None
-                    )
-                    b0 += nseg
-            try:
-                return self.apply_gradients(training_batch, grads, loss_scale)
-            finally:
-                if usample:
-                    self.metrics.update_gradient_time_cost_sec.set(
-                        time.perf_counter() - _ut0
-                    )
+                    if sc.cfg.embedding_summation:
+                        grads[sc.name] = (
+                            gbase[b0 : b0 + B] if gbase is not None else None
+                        )
+                        b0 += B
+            return self._apply_slot_grads(training_batch, grads, loss_scale)
 
-        from persia_amd.ops import native as _native
-
-        C = _native()
-        for gi, group in enumerate(training_batch._groups):
-            buf = None  # allocated lazily: the fused path never needs it
-            if sum_base_grads is not None:
-                gbase = sum_base_grads[gi]
-            else:
-                gbase = group.sum_base.grad if group.sum_base is not None else None
+        for group, gbase in zip(groups, sum_base_grads):
+            if gbase is None and not raw_grads:
+                # no sum-base grad and no raw grads: skip the group (a
+                # zero-grad optimizer application would still move Adam /
+                # Adagrad state — reference skips the slot instead)
+                continue
+            store = self.stores[group.dim]
             if gbase is not None:
-                # NaN gradients flow into buf and are skipped ROW-wise by the
-                # update kernel (store.update_gradients) — no isnan pass here
-                has_sqrt = group.sqrt_mask is not None and bool(group.sqrt_mask.any())
-                if loss_scale == 1.0 and not has_sqrt:
-                    seg_scale = self._empty_f32()
-                else:
-                    n_segs = gbase.shape[0]
-                    seg_scale = torch.full(
-                        (n_segs,), 1.0 / loss_scale, device=self.device
-                    )
-                    if has_sqrt:
-                        seg_scale = seg_scale * torch.where(
-                            group.sqrt_mask,
-                            group.seg_lens.clamp(min=1.0).rsqrt(),
-                            torch.ones_like(group.seg_lens),
+                # NaN gradients flow on and are skipped ROW-wise by the
+                # update kernels — no isnan pass here
+                seg_scale = self._seg_scale(group, loss_scale)
+                if store.fused_native and not raw_grads:
+                    if (
+                        group.a2a_idx is not None
+                        and self.wire_dtype == torch.float16
+                    ):
+                        # fused distributed backward: zero host syncs
+                        self._a2a_backward_native(group, gbase, seg_scale, store)
+                        continue
+                    if not self.dist.distributed:
+                        # fused native backward: scatter + optimizer in one call
+                        store.update_local(
+                            gbase, group.perm, group.ustarts, group.seg_id,
+                            seg_scale, group.uniq_keys, group.u_count,
                         )
-                store = self.stores[group.dim]
-                if (
-                    group.a2a_idx is not None
-                    and not raw_grads
-                    and hasattr(store, "_opt_code")
-                    and self.wire_dtype == torch.float16
-                ):
-                    # fused distributed backward: indexed scatter straight
-                    # into the a2a send layout, even a2a, owner-side fused
-                    # dedup+optimizer — zero host syncs
-                    self._a2a_backward_native(group, gbase, seg_scale, store, C)
-                    continue
-                if (
-                    not self.dist.distributed
-                    and not raw_grads
-                    and hasattr(store, "_opt_code")  # HipEmbeddingStore
-                ):
-                    # fused native backward: scatter + optimizer in one call
-                    powers = store._adam_step_powers()
-                    b1p, b2p = powers if powers else (0.0, 0.0)
-                    C.update_local(
-                        gbase.contiguous(), group.perm, group.ustarts,
-                        group.seg_id, seg_scale, group.uniq_keys,
-                        store.keys, store.ticks, store.arena, group.dim,
-                        store._opt_code, store._opt_params(), float(b1p),
-                        float(b2p), float(self.hyper.weight_bound),
-                        store._skipped,
-                        group.u_count
-                        if group.u_count is not None
-                        else self._empty_i64(),
-                    )
-                    if self.incremental is not None:
-                        self.incremental.record_keys(
-                            group.uniq_keys, group.u_count
-                        )
-                    continue
-                self._materialize_group(group)
+                        if self.incremental is not None:
+                            self.incremental.record_keys(
+                                group.uniq_keys, group.u_count
+                            )
+                        continue
+            self._materialize_group(group)
+            U = group.uniq_keys.numel()
+            if gbase is not None:
                 buf = torch.empty(
-                    group.uniq_keys.numel(), group.dim,
-                    dtype=torch.float32, device=self.device,
+                    U, group.dim, dtype=torch.float32, device=self.device
                 )
-                C.grad_scatter(
+                self._C.grad_scatter(
                     gbase.contiguous(), group.perm, group.ustarts,
                     group.seg_id, seg_scale, buf, 0,
                 )
             else:
-                if not raw_grads:
-                    # no sum-base grad and no raw grads: skip the group (a
-                    # zero-grad optimizer application would still move Adam /
-                    # Adagrad state — reference skips the slot instead)
-                    continue
-                self._materialize_group(group)
                 buf = torch.zeros(
-                    group.uniq_keys.numel(), group.dim,
-                    dtype=torch.float32, device=self.device,
+                    U, group.dim, dtype=torch.float32, device=self.device
                 )
-            # raw slots add on top (buf fully written above)
-            if raw_grads:
-                for sc in group.slots:
-                    if sc.cfg.embedding_summation:
-                        continue
-                    g = raw_grads.get(sc.name)
-                    if g is None:
-                        continue
-                    if bool(torch.isnan(g).any()):
-                        self.nan_grad_batches += 1
-                        continue
-                    gf = g.float()
-                    if loss_scale != 1.0:
-                        gf = gf / loss_scale
-                    rounds = sc.cfg.hash_stack_rounds
-                    if sc.cfg.sqrt_scaling and rounds > 0:
-                        gf = gf / float(np.sqrt(rounds))
-                    buf.index_add_(0, sc.slot_uniq_global, gf)
+            if raw_grads:  # raw slots add on top (buf fully written above)
+                self._add_raw_grads(group, raw_grads, loss_scale, buf)
             self._route_and_update(group, buf)
-        if usample:
-            # host-side issue+wait time of the whole gradient push (the
-            # reference's update_gradient_time_cost_sec, mod.rs:83-100)
-            self.metrics.update_gradient_time_cost_sec.set(
-                time.perf_counter() - _ut0
-            )
 
     # ------------------------------------------------------------ checkpoint
 
@@ -1690,9 +1596,7 @@ class ForwardPipeline:
             # PA_SPARSE_PRIORITY=-1 raises the lookup stream's scheduling
             # priority: on presets where the sparse stream is the critical
             # path (spill/dim-8 tables) the dense replay otherwise starves it
-            import os as _os
-
-            prio = int(_os.environ.get("PA_SPARSE_PRIORITY", "0"))
+            prio = int(os.environ.get("PA_SPARSE_PRIORITY", "0"))
             stream = torch.cuda.Stream(device=self.engine.device, priority=prio)
         import heapq
 

@@ -170,6 +170,10 @@ def _adapt_row_width(inner: np.ndarray, row_width: int,
 class EmbeddingStoreBase:
     """One rank's shard for one dim-group of slots."""
 
+    # True where the backend has the fused entry points the engine's
+    # sync-free paths call: lookup_local, update_local, scatter_update
+    fused_native = False
+
     def __init__(
         self,
         dim: int,
@@ -271,6 +275,11 @@ class EmbeddingStoreBase:
         mixed old/new row, which the bounded-staleness freshness contract
         tolerates (the reference holds per-sign locks instead)."""
         raise NotImplementedError
+
+    def skip_counters(self) -> Optional[torch.Tensor]:
+        """Device-side i32[2] (missing-key, NaN-row) update skip counters for
+        the metrics harvest, or None where skips are returned host-side."""
+        return None
 
     def _spill_export(self):
         """Host-tier rows for checkpointing (spilled rows are table state)."""
@@ -495,6 +504,8 @@ class HipEmbeddingStore(EmbeddingStoreBase):
     allocator so it coexists with the dense model); kernels mutate them in
     place."""
 
+    fused_native = True
+
     def __init__(self, dim, capacity, optimizer, hyper, device, spill_capacity: int = 0):
         super().__init__(dim, capacity, optimizer, hyper, device, spill_capacity)
         from persia_amd.ops import native
@@ -518,10 +529,15 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         self._imported = torch.zeros(1, dtype=torch.int64, device=device)
         self._import_offered = 0
         self.evicted_total = 0  # host-side eviction count (spill drains)
+        # "argument absent" sentinels of the native calls: no device-side
+        # unique count (keys are exact), no per-segment scale (all ones), no
+        # eviction log (no spill tier)
+        self.no_count = torch.empty(0, dtype=torch.int64, device=device)
+        self._no_scale = torch.empty(0, dtype=torch.float32, device=device)
         self._no_evict = (
-            torch.empty(0, dtype=torch.int64, device=device),
+            self.no_count,
             torch.empty(0, dtype=torch.int32, device=device),
-            torch.empty(0, dtype=torch.float32, device=device),
+            self._no_scale,
         )
 
     def _evict_buffers(self, n: int):
@@ -585,6 +601,28 @@ class HipEmbeddingStore(EmbeddingStoreBase):
             return [o.lr, o.betas[0], o.betas[1], o.eps, 0.0, 0.0]
         raise ValueError(o.kind)
 
+    def _lookup_args(self, train: bool, tick: int):
+        """The argument run every native lookup shares (after the table
+        tensors): dim, train, tick, init range, admit probability, optimizer
+        state init and width."""
+        lo, hi = self.hyper.emb_initialization
+        return (
+            self.dim, int(train), tick, float(lo), float(hi),
+            float(self.hyper.admit_probability),
+            float(self.optimizer.state_init(self.dim)), self.opt_space,
+        )
+
+    def _update_args(self):
+        """The argument run every native update shares: dim, optimizer code
+        and params, Adam beta powers, weight bound, skip counters.  Steps the
+        Adam powers, so it is called exactly once per update call."""
+        powers = self._adam_step_powers()
+        b1p, b2p = powers if powers else (0.0, 0.0)
+        return (
+            self.dim, self._opt_code, self._opt_params(), float(b1p),
+            float(b2p), float(self.hyper.weight_bound), self._skipped,
+        )
+
     def __len__(self) -> int:
         return int((self.keys != 0).sum().item())
 
@@ -612,28 +650,38 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         self._restore_tick = tick
         if not len(self.spill) or keys.numel() == 0:
             return
-        uc = (
-            u_count
-            if u_count is not None
-            else torch.empty(0, dtype=torch.int64, device=self.device)
-        )
         self._drain_pending()
+        # the log holds the imports' evictions only; drained at once
+        ev = self._spill_phase1(
+            keys, tick, u_count if u_count is not None else self.no_count, 0
+        )
+        if ev is not None:
+            self._drain_evictions(ev)
+
+    def _spill_phase1(self, keys: torch.Tensor, tick: int, uc: torch.Tensor,
+                      log_rows: int):
+        """Probe ``keys``, fetch the misses from the host tier and import the
+        found rows into HBM.  -> the eviction log the import wrote (sized
+        ``log_rows`` + rows imported: imports can evict too), or None when
+        nothing was imported.  The ``keys[slots < 0]`` readback syncs only the
+        caller's stream."""
         slots = self._C.store_probe(self.keys, self.ticks, keys, tick, uc)
-        miss_keys = keys[slots < 0]  # syncs ONLY the caller's (probe) stream
-        if miss_keys.numel():
-            miss_np = miss_keys.cpu().numpy().view(np.uint64)
-            rows, found = self.spill.fetch(miss_np)
-            if found.any():
-                ev = self._evict_buffers(int(found.sum()))
-                found_keys = torch.from_numpy(
-                    miss_np[found].view(np.int64).copy()
-                ).to(self.device)
-                rows_t = torch.from_numpy(rows[found]).to(self.device)
-                self._C.store_import(
-                    self.keys, self.ticks, self.arena, found_keys, rows_t,
-                    tick, *ev,
-                )
-                self._drain_evictions(ev)
+        miss_keys = keys[slots < 0]
+        if not miss_keys.numel():
+            return None
+        miss_np = miss_keys.cpu().numpy().view(np.uint64)
+        rows, found = self.spill.fetch(miss_np)
+        if not found.any():
+            return None
+        ev = self._evict_buffers(log_rows + int(found.sum()))
+        found_keys = torch.from_numpy(
+            miss_np[found].view(np.int64).copy()
+        ).to(self.device)
+        rows_t = torch.from_numpy(rows[found]).to(self.device)
+        self._C.store_import(
+            self.keys, self.ticks, self.arena, found_keys, rows_t, tick, *ev
+        )
+        return ev
 
     def lookup(
         self, keys: torch.Tensor, train: bool,
@@ -649,52 +697,19 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         else:
             tick = self.next_tick()
         n = keys.numel()
-        uc = (
-            u_count
-            if u_count is not None
-            else torch.empty(0, dtype=torch.int64, device=self.device)
-        )
+        uc = u_count if u_count is not None else self.no_count
         ev = self._no_evict
         if self.spill is not None and train and n:
             self._drain_pending()
             ev = self._evict_buffers(n)
-        if (not restored and self.spill is not None and train and n
-                and len(self.spill)):
-            # spill phase 1 inline (engine did not pre-restore)
-            slots = self._C.store_probe(self.keys, self.ticks, keys, tick, uc)
-            miss_keys = keys[slots < 0]
-            if miss_keys.numel():
-                miss_np = miss_keys.cpu().numpy().view(np.uint64)
-                rows, found = self.spill.fetch(miss_np)
-                if found.any():
-                    # re-size the log: imports can evict too
-                    ev = self._evict_buffers(n + int(found.sum()))
-                    found_keys = torch.from_numpy(
-                        miss_np[found].view(np.int64).copy()
-                    ).to(self.device)
-                    rows_t = torch.from_numpy(rows[found]).to(self.device)
-                    self._C.store_import(
-                        self.keys, self.ticks, self.arena, found_keys, rows_t,
-                        tick, *ev,
-                    )
+            if not restored and len(self.spill):
+                # spill phase 1 inline (engine did not pre-restore): one log
+                # for the imports' and the lookup's evictions, drained below
+                ev = self._spill_phase1(keys, tick, uc, n) or ev
         out = torch.empty(n, self.dim, dtype=torch.float32, device=self.device)
-        lo, hi = self.hyper.emb_initialization
         self._C.store_lookup(
-            self.keys,
-            self.ticks,
-            self.arena,
-            keys,
-            out,
-            self.dim,
-            int(train),
-            tick,
-            float(lo),
-            float(hi),
-            float(self.hyper.admit_probability),
-            float(self.optimizer.state_init(self.dim)),
-            self.opt_space,
-            *ev,
-            uc,
+            self.keys, self.ticks, self.arena, keys, out,
+            *self._lookup_args(train, tick), *ev, uc,
         )
         self._drain_evictions(ev)
         return out
@@ -704,38 +719,59 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         """Padded-a2a owner lookup: key 0 entries (bucket padding) return
         zeros and never claim slots (kernel-level skip); output is the wire
         dtype directly (fused f16 cast in init_gather)."""
-        tick = self.next_tick()
-        n = keys.numel()
-        out = torch.empty(n, self.dim, dtype=wire_dtype, device=self.device)
-        lo, hi = self.hyper.emb_initialization
+        out = torch.empty(
+            keys.numel(), self.dim, dtype=wire_dtype, device=self.device
+        )
         self._C.store_lookup(
-            self.keys, self.ticks, self.arena, keys, out, self.dim,
-            int(train), tick, float(lo), float(hi),
-            float(self.hyper.admit_probability),
-            float(self.optimizer.state_init(self.dim)), self.opt_space,
-            *self._no_evict,
-            torch.empty(0, dtype=torch.int64, device=self.device),
+            self.keys, self.ticks, self.arena, keys, out,
+            *self._lookup_args(train, self.next_tick()), *self._no_evict,
+            self.no_count,
         )
         return out
 
+    def lookup_local(self, values: torch.Tensor, slot_starts: torch.Tensor,
+                     prefixes: torch.Tensor, spacing_arg: int,
+                     cat_offsets: torch.Tensor, seg_scale: torch.Tensor,
+                     train: bool):
+        """The whole single-GPU lookup of an all-single-ID sum group in one
+        native call: sign prep, padded dedup, probe/insert, gather and the
+        fused segment sum over the uploaded raw ``values``.
+        -> (sums, uniq, inverse, perm, ustarts, u_count)."""
+        return self._C.lookup_local(
+            values, slot_starts, prefixes, spacing_arg, cat_offsets, seg_scale,
+            self.keys, self.ticks, self.arena,
+            *self._lookup_args(train, self.next_tick()),
+        )
+
+    def update_local(self, gbase, perm, ustarts, seg_id, seg_scale, uniq,
+                     u_count: Optional[torch.Tensor]) -> None:
+        """Fused local backward: ordered per-unique reduction of the segment
+        gradients ``gbase`` and the optimizer step, in one call."""
+        self._C.update_local(
+            gbase.contiguous(), perm, ustarts, seg_id, seg_scale, uniq,
+            self.keys, self.ticks, self.arena, *self._update_args(),
+            u_count if u_count is not None else self.no_count,
+        )
+
+    def scatter_update(self, uniq, grads, perm, ustarts, seg_id,
+                       u_count: torch.Tensor) -> None:
+        """Owner-side fused backward of the padded a2a: reduce the received
+        per-position ``grads`` per unique key and apply the optimizer.
+        Positions whose key is 0 (bucket padding) are skipped on the key."""
+        self._C.scatter_update(
+            self.keys, self.ticks, self.arena, uniq, grads, perm, ustarts,
+            seg_id, self._no_scale, *self._update_args(), u_count,
+        )
+
     def update_gradients(self, keys: torch.Tensor, grads: torch.Tensor) -> int:
-        powers = self._adam_step_powers()
-        b1p, b2p = powers if powers else (0.0, 0.0)
         self._C.store_update(
-            self.keys,
-            self.ticks,
-            self.arena,
-            keys,
-            grads.float().contiguous(),
-            self.dim,
-            self._opt_code,
-            self._opt_params(),
-            float(b1p),
-            float(b2p),
-            float(self.hyper.weight_bound),
-            self._skipped,
+            self.keys, self.ticks, self.arena, keys,
+            grads.float().contiguous(), *self._update_args(),
         )
         return 0  # skipped count is accumulated device-side (no hot-path sync)
+
+    def skip_counters(self) -> torch.Tensor:
+        return self._skipped
 
     def skipped_count(self) -> int:
         return int(self._skipped[0].item())
@@ -748,8 +784,7 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         ks[ks == EMPTY_KEY] = _ZERO_REMAP
         keys_t = torch.from_numpy(ks.view(np.int64)).to(self.device)
         slots = self._C.store_probe(
-            self.keys, self.ticks, keys_t, self.tick,
-            torch.empty(0, dtype=torch.int64, device=self.device),
+            self.keys, self.ticks, keys_t, self.tick, self.no_count
         )
         found = slots >= 0
         inner = self.arena[slots[found]].cpu().numpy()
