@@ -309,8 +309,8 @@ using bf16x4t = __attribute__((ext_vector_type(4))) __bf16;
 
 __global__ __launch_bounds__(256) void wgrad_tr_kernel(
     const short* __restrict__ dC, const short* __restrict__ A,
-    float* __restrict__ dW, int M, int N, int K, int splitm, int ldw,
-    int kmax, int accum) {
+    float* __restrict__ dW, int M, int N, int K, int splitm, int m_chunk,
+    int ldw, int kmax, int accum) {
   constexpr int MT = 64;  // m-rows per buffer
   // panel layout per image: [8 panels][MT rows][16 cols] bf16 = 16 KB
   __shared__ short lds_c[2][8 * MT * 16];
@@ -325,8 +325,12 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(
   const int wr = wave / 2, wc = wave % 2;
   const int fi = lane & 15;
 
-  const int m_chunk = ((M + splitm - 1) / splitm + MT - 1) / MT * MT;
+  // m_chunk (a multiple of MT) and splitm come from wgrad_plan, which makes
+  // every part non-empty.  The staging below has no row guard, so a part
+  // that starts past the end must not reach it; the test is block-uniform,
+  // hence safe ahead of the barriers.
   const int m_begin = m_part * m_chunk;
+  if (m_begin >= M) return;
   const int m_end = min(M, m_begin + m_chunk);
 
   // glds chunks: wave w stages panels [w*2, w*2+2) of each image (4 x 1 KB
@@ -651,8 +655,8 @@ constexpr int WLD = WTM + PAD;
 
 __global__ __launch_bounds__(256) void wgrad_kernel(
     const short* __restrict__ dC, const short* __restrict__ A,
-    float* __restrict__ dW, int M, int N, int K, int splitm, int ldw,
-    int kmax, int accum) {
+    float* __restrict__ dW, int M, int N, int K, int splitm, int m_chunk,
+    int ldw, int kmax, int accum) {
   __shared__ short lds_dct[2][64 * WLD];  // [n][m]
   __shared__ short lds_at[2][64 * WLD];   // [k][m]
   // staging pieces: [WTM rows x 64 cols] / (256 threads x 8 shorts) = 2 each
@@ -669,7 +673,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(
   const int fi = lane & 15;
   const int fk8 = (lane >> 4) * 8;
 
-  const int m_chunk = ((M + splitm - 1) / splitm + WTM - 1) / WTM * WTM;
+  // m_chunk (a multiple of WTM) and splitm come from wgrad_plan
   const int m_begin = m_part * m_chunk;
   const int m_end = min(M, m_begin + m_chunk);
 
@@ -1083,8 +1087,15 @@ std::string gemm_nt_config(int64_t M, int64_t N, int64_t K, int64_t trans_b) {
 // torch.zeros).  Falls back to the unfused pair for non-pow2 N.
 torch::Tensor relu_bwd_bias(torch::Tensor g, torch::Tensor out,
                             torch::Tensor db) {
+  TORCH_CHECK(g.scalar_type() == torch::kBFloat16 && g.dim() == 2 &&
+                  g.is_contiguous() && out.is_contiguous(),
+              "relu_bwd_bias: g must be contiguous bf16 [M, N]");
+  TORCH_CHECK(out.scalar_type() == g.scalar_type() &&
+                  out.sizes() == g.sizes() && out.device() == g.device(),
+              "relu_bwd_bias: g and out must have the same shape and dtype");
   const int64_t M = g.size(0), N = g.size(1);
-  TORCH_CHECK(db.scalar_type() == torch::kFloat32 && db.numel() == N);
+  TORCH_CHECK(db.scalar_type() == torch::kFloat32 && db.numel() == N &&
+              db.is_contiguous() && db.device() == g.device());
   const bool pow2 = (N & (N - 1)) == 0 && N >= 8 && N <= 8192;
   TORCH_CHECK(pow2, "relu_bwd_bias: power-of-two N only");
   auto g_eff = torch::empty_like(g);
@@ -1161,10 +1172,13 @@ void bias_grad_into(torch::Tensor dC, torch::Tensor out) {
   bias_grad_launch(dC, out);
 }
 
-// dW [N,K] f32 = dC^T @ A
-static void wgrad_launch(torch::Tensor dC, torch::Tensor A, torch::Tensor out,
-                         int ldw, int kmax, int accum) {
-  const int M = (int)dC.size(0), N = (int)dC.size(1), K = (int)A.size(1);
+// Kernel choice and M split shared by both wgrad launchers.
+struct WgradPlan {
+  bool tr;
+  int tiles, splitm, chunk;
+};
+
+static WgradPlan wgrad_plan(int M, int N, int K) {
   static const bool tr_on = [] {
     const char* e = getenv("PA_WGRAD_TR");
     return !e || atoi(e) != 0;
@@ -1172,31 +1186,77 @@ static void wgrad_launch(torch::Tensor dC, torch::Tensor A, torch::Tensor out,
   // cutover (tools/wgrad_tr_probe.py): the 128x128-tile tr kernel wins only
   // when its own grid fills the chip (1024x1024: 48.7 vs 66.0 us); below
   // that the v1 64x64 tiles + split-M keep more CUs busy
-  if (tr_on && M % 64 == 0 && N % 128 == 0 && K % 128 == 0 &&
-      (N / 128) * (K / 128) >= 64) {
-    const int tiles2 = (N / 128) * (K / 128);
-    int splitm = 1;
-    while (tiles2 * splitm < 512 && splitm < 64 && (M / (splitm * 2)) >= 64)
-      splitm *= 2;
-    if (splitm > 1 && !accum) out.zero_();
-    hipLaunchKernelGGL(wgrad_tr_kernel, dim3(tiles2 * splitm), dim3(256), 0,
+  WgradPlan p;
+  p.tr = tr_on && M % 64 == 0 && N % 128 == 0 && K % 128 == 0 &&
+         (N / 128) * (K / 128) >= 64;
+  p.tiles = p.tr ? (N / 128) * (K / 128) : ((N + 63) / 64) * ((K + 63) / 64);
+  // split M (atomicAdd fan-in) until the grid fills the chip, keeping at
+  // least min_rows rows per part
+  const int min_rows = p.tr ? 64 : 32;
+  int want = 1;
+  while (p.tiles * want < 512 && want < 64 && (M / (want * 2)) >= min_rows)
+    want *= 2;
+  // Both kernels stage 64 m-rows per step (MT / WTM), so a part's chunk is
+  // rounded UP to a multiple of 64 — and the part count is then re-derived
+  // from the rounded chunk: splitm = ceil(M / chunk), which makes
+  // (splitm - 1) * chunk < M, i.e. every part starts inside the matrix.
+  // (`want` parts of the rounded chunk can overshoot: M=320 wants 4 parts of
+  // 80 -> 128 rows, and a 4th part would start at row 384.)  The tr kernel
+  // stages without a row guard, in whole 64-row steps from m_begin up to
+  // min(M, m_begin + chunk); with M, chunk and hence m_begin all multiples
+  // of 64 and m_begin < M, every staged step [m, m + 64) ends at or before
+  // M, so no load addresses a row >= M.
+  p.chunk = ((M + want - 1) / want + 63) / 64 * 64;
+  p.splitm = (M + p.chunk - 1) / p.chunk;
+  return p;
+}
+
+// Which wgrad kernel and M split a shape gets, e.g. "tr:splitm=4:chunk=128"
+// or "v1:splitm=2:chunk=64" (host only; tests sweep it).
+std::string wgrad_config(int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1);
+  const WgradPlan p = wgrad_plan((int)M, (int)N, (int)K);
+  return std::string(p.tr ? "tr" : "v1") + ":splitm=" +
+         std::to_string(p.splitm) + ":chunk=" + std::to_string(p.chunk);
+}
+
+static void wgrad_check_operands(const torch::Tensor& dC,
+                                 const torch::Tensor& A) {
+  TORCH_CHECK(dC.scalar_type() == torch::kBFloat16 &&
+                  A.scalar_type() == torch::kBFloat16,
+              "wgrad: operands must be bf16");
+  TORCH_CHECK(dC.dim() == 2 && A.dim() == 2 && dC.is_contiguous() &&
+                  A.is_contiguous(),
+              "wgrad: operands must be contiguous 2-D");
+  TORCH_CHECK(dC.device() == A.device(), "wgrad: operands on different devices");
+  TORCH_CHECK(dC.size(0) == A.size(0) && dC.size(0) >= 1,
+              "wgrad: dC and A row counts differ");
+  // the v1 kernel's 8-wide vector loads are guarded at their first element
+  TORCH_CHECK(dC.size(1) % 8 == 0 && A.size(1) % 8 == 0 && dC.size(1) >= 8 &&
+                  A.size(1) >= 8,
+              "wgrad: N and K must be multiples of 8");
+}
+
+// dW [N,K] f32 = dC^T @ A
+static void wgrad_launch(torch::Tensor dC, torch::Tensor A, torch::Tensor out,
+                         int ldw, int kmax, int accum) {
+  const int M = (int)dC.size(0), N = (int)dC.size(1), K = (int)A.size(1);
+  const WgradPlan p = wgrad_plan(M, N, K);
+  if (p.splitm > 1 && !accum) out.zero_();
+  if (p.tr)
+    hipLaunchKernelGGL(wgrad_tr_kernel, dim3(p.tiles * p.splitm), dim3(256), 0,
                        dcur_stream(), (const short*)dC.data_ptr(),
                        (const short*)A.data_ptr(), out.data_ptr<float>(), M, N,
-                       K, splitm, ldw, kmax, accum);
-    return;
-  }
-  const int tiles = ((N + 63) / 64) * ((K + 63) / 64);
-  int splitm = 1;
-  while (tiles * splitm < 512 && splitm < 64 && (M / (splitm * 2)) >= 32)
-    splitm *= 2;
-  if (splitm > 1 && !accum) out.zero_();
-  hipLaunchKernelGGL(wgrad_kernel, dim3(tiles * splitm), dim3(256), 0,
-                     dcur_stream(), (const short*)dC.data_ptr(),
-                     (const short*)A.data_ptr(), out.data_ptr<float>(), M, N,
-                     K, splitm, ldw, kmax, accum);
+                       K, p.splitm, p.chunk, ldw, kmax, accum);
+  else
+    hipLaunchKernelGGL(wgrad_kernel, dim3(p.tiles * p.splitm), dim3(256), 0,
+                       dcur_stream(), (const short*)dC.data_ptr(),
+                       (const short*)A.data_ptr(), out.data_ptr<float>(), M, N,
+                       K, p.splitm, p.chunk, ldw, kmax, accum);
 }
 
 torch::Tensor wgrad(torch::Tensor dC, torch::Tensor A) {
+  wgrad_check_operands(dC, A);
   const int N = (int)dC.size(1), K = (int)A.size(1);
   auto dW = torch::empty(
       {N, K}, torch::TensorOptions().dtype(torch::kFloat32).device(A.device()));
@@ -1209,8 +1269,12 @@ torch::Tensor wgrad(torch::Tensor dC, torch::Tensor A) {
 // no dW materialization, no cast, no pad-column slice, no AccumulateGrad
 // add.  `out` may be narrower than A (kmax < K drops the zero pad columns).
 void wgrad_into(torch::Tensor dC, torch::Tensor A, torch::Tensor out) {
-  TORCH_CHECK(out.scalar_type() == torch::kFloat32 && out.is_contiguous());
-  TORCH_CHECK(out.size(0) == dC.size(1) && out.size(1) <= A.size(1));
+  wgrad_check_operands(dC, A);
+  TORCH_CHECK(out.scalar_type() == torch::kFloat32 && out.is_contiguous() &&
+                  out.dim() == 2 && out.device() == A.device(),
+              "wgrad_into: out must be contiguous 2-D f32 on the operands' device");
+  TORCH_CHECK(out.size(0) == dC.size(1) && out.size(1) <= A.size(1),
+              "wgrad_into: out must be [N, kmax <= K]");
   wgrad_launch(dC, A, out, (int)out.size(1), (int)out.size(1), 1);
 }
 
@@ -1253,6 +1317,8 @@ void init_dense(pybind11::module_& m) {
   m.def("bce_bwd", &bce_bwd, "fused BCE-with-logits backward");
   m.def("bias_grad", &bias_grad, "column-sum bias gradient");
   m.def("wgrad", &wgrad, "dW = dC^T @ A (f32 out)");
+  m.def("wgrad_config", &wgrad_config,
+        "wgrad kernel and M split the dispatch picks for a shape");
   m.def("wgrad_into", &wgrad_into,
         "dW accumulated straight into a flat f32 grad slot");
   m.def("bias_grad_into", &bias_grad_into,

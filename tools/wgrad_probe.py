@@ -11,8 +11,4 @@ for (M, N, K) in [(512,256,224),(512,256,256),(1024,256,224),(512,64,64),(512,25
     dW = C.wgrad(dC, A)
     ref = dC.float().t() @ A.float()
     err = (dW - ref).abs().max().item()
-    tiles = ((N+63)//64)*((K+63)//64)
-    splitm = 1
-    while tiles * splitm < 512 and splitm < 64 and (M // (splitm*2)) >= 32:
-        splitm *= 2
-    print(f"M{M} N{N} K{K} tiles{tiles} splitm{splitm} err {err:.4f}", flush=True)
+    print(f"M{M} N{N} K{K} {C.wgrad_config(M, N, K)} err {err:.4f}", flush=True)
