@@ -187,6 +187,11 @@ class _GroupCtx:
     perm: torch.Tensor  # [nnz] sort permutation (ordered grad scatter)
     ustarts: torch.Tensor  # [U+1] unique boundaries in sorted order
     u_count: Optional[torch.Tensor] = None  # [1] i64 device unique count
+    # update hints of the one-call lookup (None on every other path), [nnz]
+    # i64, valid below u_count: the slot each unique key was given, and the
+    # gradient row of a key with a single position (-1: none)
+    slot_hint: Optional[torch.Tensor] = None
+    src_hint: Optional[torch.Tensor] = None
     slots: List[_SlotCtx] = field(default_factory=list)
     # fused sum-slot segment space (sum slots occupy positions [0, sum_end))
     cat_offsets: Optional[torch.Tensor] = None  # [n_sum_segs+1]
@@ -330,7 +335,8 @@ class PersiaTrainingBatch:
         for g in self._groups:
             a2a_owner = g.a2a_owner_dedup or ()
             for t in (g.uniq_keys, g.inverse, g.perm, g.ustarts, g.u_count,
-                      g.sum_base, g.cat_offsets, g.seg_id, g.seg_lens,
+                      g.slot_hint, g.src_hint, g.sum_base, g.cat_offsets,
+                      g.seg_id, g.seg_lens,
                       g.sqrt_mask, g.a2a_idx, g.a2a_recv_keys, *a2a_owner):
                 if t is not None and t.is_cuda:
                     yield t
@@ -393,6 +399,8 @@ class EmbeddingEngine:
         self.nan_grad_batches = 0
         self._plans = {}
         self._empty_scale = torch.empty(0, dtype=torch.float32, device=device)
+        # lookup_local's seg_id argument when no update hints are wanted
+        self._no_seg = torch.empty(0, dtype=torch.int64, device=device)
         spacing = schema.feature_spacing
         self._spacing_arg = spacing if spacing < (1 << 63) else -1
         self.model_manager_status = "Idle"
@@ -409,6 +417,10 @@ class EmbeddingEngine:
         # (copy in place of the collectives) for single-GPU tests/profiling
         self._fused_dist = os.environ.get("PA_FUSED_DIST", "1") == "1"
         self._force_dist = os.environ.get("PA_FORCE_DIST", "0") == "1"
+        # PA_UPDATE_HINTS (default on): the fused local update takes the
+        # lookup's slot/source hints; 0 asks for and passes none (A/B switch,
+        # same results)
+        self._update_hints = os.environ.get("PA_UPDATE_HINTS", "1") != "0"
         # PA_ROCTX=1: named roctx ranges around the pipeline stages for
         # rocprofv3 --marker-trace (torch.cuda.nvtx IS roctx on ROCm);
         # off by default so the hot loop never pays the marker calls
@@ -919,10 +931,13 @@ class EmbeddingEngine:
             # probe/insert, gather and the fused segment-sum)
             if timing:
                 t0 = self._tick("prep", t0)
-            sums, uniq, inverse, perm, ustarts, u_count = store.lookup_local(
+            (sums, uniq, inverse, perm, ustarts, u_count, slot_hint,
+             src_hint) = store.lookup_local(
                 self._upload_group(dim, feats, batch), plan.slot_starts,
                 plan.prefixes, self._spacing_arg, plan.cat_offsets,
-                plan.empty_scale, train,
+                plan.empty_scale,
+                plan.seg_id if train and self._update_hints else self._no_seg,
+                train,
             )
         else:
             # spill tier (single GPU, training): upload..dedup plus the
@@ -957,6 +972,9 @@ class EmbeddingEngine:
             cat_offsets=plan.cat_offsets, seg_id=plan.seg_id,
             n_sum_slots=plan.S,
         )
+        if one_call:
+            if slot_hint.numel():  # both empty when none were asked for
+                group.slot_hint, group.src_hint = slot_hint, src_hint
         if padded:
             # rows over the capacity-padded even a2a (no host count syncs
             # anywhere); the unpack gather is composed into `inverse` so
@@ -1456,6 +1474,7 @@ class EmbeddingEngine:
                         store.update_local(
                             gbase, group.perm, group.ustarts, group.seg_id,
                             seg_scale, group.uniq_keys, group.u_count,
+                            group.slot_hint, group.src_hint,
                         )
                         if self.incremental is not None:
                             self.incremental.record_keys(

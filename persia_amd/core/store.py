@@ -732,25 +732,35 @@ class HipEmbeddingStore(EmbeddingStoreBase):
     def lookup_local(self, values: torch.Tensor, slot_starts: torch.Tensor,
                      prefixes: torch.Tensor, spacing_arg: int,
                      cat_offsets: torch.Tensor, seg_scale: torch.Tensor,
-                     train: bool):
+                     seg_id: torch.Tensor, train: bool):
         """The whole single-GPU lookup of an all-single-ID sum group in one
         native call: sign prep, padded dedup, probe/insert, gather and the
         fused segment sum over the uploaded raw ``values``.
-        -> (sums, uniq, inverse, perm, ustarts, u_count)."""
+        -> (sums, uniq, inverse, perm, ustarts, u_count, slot_hint, src_hint).
+        The last two are the update hints ``update_local`` takes back: per
+        unique key the slot the probe gave it, and through ``seg_id`` the
+        gradient row of a key with one position (-1: none)."""
         return self._C.lookup_local(
             values, slot_starts, prefixes, spacing_arg, cat_offsets, seg_scale,
-            self.keys, self.ticks, self.arena,
+            seg_id, self.keys, self.ticks, self.arena,
             *self._lookup_args(train, self.next_tick()),
         )
 
     def update_local(self, gbase, perm, ustarts, seg_id, seg_scale, uniq,
-                     u_count: Optional[torch.Tensor]) -> None:
+                     u_count: Optional[torch.Tensor],
+                     slot_hint: Optional[torch.Tensor] = None,
+                     src_hint: Optional[torch.Tensor] = None) -> None:
         """Fused local backward: ordered per-unique reduction of the segment
-        gradients ``gbase`` and the optimizer step, in one call."""
+        gradients ``gbase`` and the optimizer step, in one call.  The hints
+        (``lookup_local``, both or neither) only shorten the kernel's
+        dependent loads; the result is the same bits without them."""
+        hinted = slot_hint is not None and src_hint is not None
         self._C.update_local(
             gbase.contiguous(), perm, ustarts, seg_id, seg_scale, uniq,
             self.keys, self.ticks, self.arena, *self._update_args(),
             u_count if u_count is not None else self.no_count,
+            slot_hint if hinted else self.no_count,
+            src_hint if hinted else self.no_count,
         )
 
     def scatter_update(self, uniq, grads, perm, ustarts, seg_id,

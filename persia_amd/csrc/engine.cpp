@@ -17,13 +17,12 @@ void store_lookup(torch::Tensor table_keys, torch::Tensor ticks,
                   int64_t opt_space, torch::Tensor evict_keys,
                   torch::Tensor evict_count, torch::Tensor evict_rows,
                   torch::Tensor u_count);
-void store_lookup_sums(torch::Tensor table_keys, torch::Tensor ticks,
-                       torch::Tensor arena, torch::Tensor query,
-                       torch::Tensor perm, torch::Tensor ustarts,
-                       torch::Tensor sums, int64_t dim, int64_t train,
-                       int64_t tick, double lo, double hi, double admit_prob,
-                       double state_init, int64_t opt_space,
-                       torch::Tensor u_count);
+std::vector<torch::Tensor> store_lookup_sums(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor perm, torch::Tensor ustarts,
+    torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space,
+    torch::Tensor u_count, torch::Tensor seg_id);
 void store_update(torch::Tensor table_keys, torch::Tensor ticks,
                   torch::Tensor arena, torch::Tensor query,
                   torch::Tensor grads, int64_t dim, int64_t opt,
@@ -44,7 +43,8 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
                     torch::Tensor seg_scale, int64_t dim, int64_t opt,
                     std::vector<double> params, double b1_power,
                     double b2_power, double weight_bound,
-                    torch::Tensor skipped, torch::Tensor u_count);
+                    torch::Tensor skipped, torch::Tensor u_count,
+                    torch::Tensor slot_hint, torch::Tensor src_hint);
 void dedup_finalize(torch::Tensor svals_flipped, torch::Tensor perm,
                     torch::Tensor neq, torch::Tensor rank, int64_t flip,
                     torch::Tensor inverse, torch::Tensor uniq,
@@ -109,13 +109,16 @@ std::vector<torch::Tensor> dedup_padded(torch::Tensor keys) {
 }
 
 // Single-GPU fused lookup: raw values -> per-sample summed embeddings.
-// Returns {sums f16 [n_segs, dim], uniq_keys, inverse, perm, ustarts}.
+// Returns {sums f16 [n_segs, dim], uniq_keys, inverse, perm, ustarts,
+// u_count, slot_hint, src_hint}; the last two are the update hints of
+// store_lookup_sums, computed from the group's seg_id (position -> gradient
+// row) and handed back to update_local.
 std::vector<torch::Tensor> lookup_local(
     torch::Tensor values, torch::Tensor slot_starts, torch::Tensor prefixes,
     int64_t spacing, torch::Tensor cat_offsets, torch::Tensor seg_scale,
-    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
-    int64_t dim, int64_t train, int64_t tick, double lo, double hi,
-    double admit_prob, double state_init, int64_t opt_space) {
+    torch::Tensor seg_id, torch::Tensor table_keys, torch::Tensor ticks,
+    torch::Tensor arena, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space) {
   auto keys = sign_prep(values, slot_starts, prefixes, spacing);
   auto d = dedup_padded(keys);
   auto& uniq = d[0];
@@ -132,10 +135,10 @@ std::vector<torch::Tensor> lookup_local(
   // one kernel and skip the [nnz, dim] f32 intermediate entirely
   auto sums = torch::empty(
       {nnz, dim}, torch::TensorOptions().dtype(torch::kFloat16).device(dev));
-  store_lookup_sums(table_keys, ticks, arena, uniq, perm, ustarts, sums, dim,
-                    train, tick, lo, hi, admit_prob, state_init, opt_space,
-                    u_count);
-  return {sums, uniq, inverse, perm, ustarts, u_count};
+  auto hints = store_lookup_sums(table_keys, ticks, arena, uniq, perm, ustarts,
+                                 sums, dim, train, tick, lo, hi, admit_prob,
+                                 state_init, opt_space, u_count, seg_id);
+  return {sums, uniq, inverse, perm, ustarts, u_count, hints[0], hints[1]};
 }
 
 // Single-GPU fused backward: per-segment grads -> per-sign scatter -> fused
@@ -147,12 +150,13 @@ void update_local(torch::Tensor grads, torch::Tensor perm,
                   torch::Tensor arena, int64_t dim, int64_t opt,
                   std::vector<double> params, double b1_power, double b2_power,
                   double weight_bound, torch::Tensor skipped,
-                  torch::Tensor u_count) {
+                  torch::Tensor u_count, torch::Tensor slot_hint,
+                  torch::Tensor src_hint) {
   if (grads.scalar_type() == torch::kFloat16 && dim <= 512) {
     // single fused kernel: ordered scatter + optimizer, no [U,dim] buffer
     scatter_update(table_keys, ticks, arena, uniq_keys, grads, perm, ustarts,
                    seg_id, seg_scale, dim, opt, params, b1_power, b2_power,
-                   weight_bound, skipped, u_count);
+                   weight_bound, skipped, u_count, slot_hint, src_hint);
     return;
   }
   // rare fallback (f32 grads or dim > 512): needs exact shapes — for a

@@ -81,6 +81,18 @@ __device__ __forceinline__ long long probe_find(const ull* __restrict__ keys,
   return -1;
 }
 
+// Update hint of one unique key (see scatter_update_multi_kernel): the
+// gradient row of its only position, or -1 when the key has several
+// positions or that position belongs to a raw slot — the update then walks
+// ustarts/perm/seg_id as it does without hints.
+__device__ __forceinline__ long long pa_src_hint(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ seg_id,
+    int64_t lo_p, int64_t hi_p) {
+  if (hi_p - lo_p != 1) return -1;
+  const int64_t s = seg_id[perm[lo_p]];
+  return s >= 0 ? (long long)s : -1;
+}
+
 // Eviction log (host-DRAM spill tier): a claim that evicts appends the
 // victim's key to evict_keys and remembers the log index so init_gather can
 // copy the victim ROW out before overwriting it — the engine drains the log
@@ -95,7 +107,11 @@ __global__ void probe_claim_kernel(ull* __restrict__ table_keys,
                                    ull* __restrict__ evict_keys,
                                    int* __restrict__ evict_count,
                                    long long* __restrict__ out_evict_idx,
-                                   const long long* __restrict__ n_dev) {
+                                   const long long* __restrict__ n_dev,
+                                   const int64_t* __restrict__ ustarts,
+                                   const int64_t* __restrict__ perm,
+                                   const int64_t* __restrict__ seg_id,
+                                   long long* __restrict__ src_hint) {
   // n_dev: device-side element count (padded-dedup path — the true unique
   // count is produced on-GPU so the host never synchronizes); n is the
   // grid-sizing upper bound
@@ -103,6 +119,11 @@ __global__ void probe_claim_kernel(ull* __restrict__ table_keys,
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const ull k = query[i];
+  // src_hint (optional, with ustarts/perm/seg_id): this thread's key is
+  // unique key i of a dedup, so its source hint rides along — three small
+  // loads that overlap the probe
+  if (src_hint)
+    src_hint[i] = pa_src_hint(perm, seg_id, ustarts[i], ustarts[i + 1]);
   if (k == PA_EMPTY_KEY) {
     // a2a padding sentinel (distributed recv buffers): never probed — the
     // empty key would match every free slot
@@ -696,6 +717,7 @@ __global__ void grad_scatter_idx_kernel(
 // (ordered, via the sort permutation) straight into registers, probe the
 // table, and apply the optimizer — no intermediate [U, dim] buffer.
 // Supports dim <= 8*PA_WAVE (register-resident grad row).
+template <bool HINTS>
 __global__ void scatter_update_kernel(
     ull* __restrict__ table_keys, unsigned* __restrict__ ticks,
     float* __restrict__ arena, const ull* __restrict__ uniq,
@@ -704,7 +726,9 @@ __global__ void scatter_update_kernel(
     const float* __restrict__ seg_scale, int64_t n, int dim, int row_width,
     int64_t n_buckets, int opt, float p0, float p1, float p2, float p3,
     float b1_power, float b2_power, float weight_bound,
-    int* __restrict__ skipped, const long long* __restrict__ n_dev) {
+    int* __restrict__ skipped, const long long* __restrict__ n_dev,
+    const long long* __restrict__ slot_hint,
+    const long long* __restrict__ src_hint, int64_t n_slots, int64_t n_src) {
   if (n_dev) n = *n_dev;
   const int wave = threadIdx.x / PA_WAVE;
   const int lane = threadIdx.x % PA_WAVE;
@@ -726,9 +750,32 @@ __global__ void scatter_update_kernel(
     // empty key = a2a padding: silent skip (the empty key would match every
     // free table slot in the probe)
     const bool active = (u < n) && (k != PA_EMPTY_KEY);
+    // update hints (see scatter_update_multi_kernel): the key verify, the
+    // gradient row and its scale load straight off the hints, none waiting
+    // on another.  An absent or out-of-range hint is no hint; a slot hint
+    // that fails the verify falls back to the window probe, a key without a
+    // source hint to the ustarts/perm/seg_id walk.
+    long long sh = -1, sr = -1;
+    if (HINTS && active) {
+      sh = slot_hint[u];
+      sr = src_hint[u];
+    }
+    if (sh < 0 || sh >= n_slots) sh = -1;
+    if (sr < 0 || sr >= n_src) sr = -1;
+    ull kv = PA_EMPTY_KEY;
+    if (sh >= 0) kv = table_keys[sh];
+    float hsc = 0.0f;
+    __half hg[8];
+    if (sr >= 0) {
+      hsc = seg_scale ? seg_scale[sr] : 1.0f;
+      const __half* g = grads + (int64_t)sr * dim;
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+        if (c0 + t * st < dim) hg[t] = g[c0 + t * st];
+    }
+    long long slot = (sh >= 0 && kv == k) ? sh : -1;
     // subgroup-parallel probe over the 32-slot window
-    long long slot = -1;
-    if (active) {
+    if (active && slot < 0) {
       const int64_t b = (int64_t)(k & (ull)mask);
       for (int it = 0; it * sg + c0 < WINDOW; ++it) {
         const int widx = it * sg + c0;
@@ -751,9 +798,19 @@ __global__ void scatter_update_kernel(
     float acc[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) acc[t] = 0.0f;
-    if (ok)
-      pa_reduce_positions<8>(acc, grads, perm, seg_id, seg_scale, ustarts[u],
-                          ustarts[u + 1], dim, c0, st);
+    if (ok) {
+      if (sr >= 0) {
+        // pa_reduce_positions over the key's one position
+        if (hsc != 0.0f) {
+#pragma unroll
+          for (int t = 0; t < 8; ++t)
+            if (c0 + t * st < dim) acc[t] += __half2float(hg[t]) * hsc;
+        }
+      } else {
+        pa_reduce_positions<8>(acc, grads, perm, seg_id, seg_scale, ustarts[u],
+                               ustarts[u + 1], dim, c0, st);
+      }
+    }
     bool has_nan = false;
     if (ok)
       for (int t = 0, c = c0; c < dim; c += st, ++t) has_nan |= isnan(acc[t]);
@@ -789,7 +846,8 @@ __global__ void scatter_update_kernel(
           const float a0 = __builtin_nontemporal_load(&row[dim + c]);
           const float w0 = __builtin_nontemporal_load(&row[c]);
           __builtin_nontemporal_store(pa_adagrad_w(oa, w0, a0, acc[t]), &row[c]);
-          __builtin_nontemporal_store(pa_adagrad_acc(oa, a0, acc[t]), &row[dim + c]);
+          __builtin_nontemporal_store(pa_adagrad_acc<true>(oa, a0, acc[t]),
+                                      &row[dim + c]);
         }
       }
     } else {  // Adam
@@ -807,6 +865,224 @@ __global__ void scatter_update_kernel(
   }
 }
 
+// Per-key register vector of the multi-key kernels below.
+template <int T>
+using PaAccVec = float __attribute__((ext_vector_type(T)));
+
+// Arena rows reach the helpers below through per-key pointer arrays; the
+// explicit global address space keeps their loads and stores global ones
+// (the compiler otherwise falls back to flat addressing for them).
+using PaGlobalF = __attribute__((address_space(1))) float;
+
+// The arena values of Q rows held in registers between their load and the
+// optimizer step: weights, up to two per-column state vectors, and the
+// vectorwise-shared Adagrad scalar.  Lane `lane` owns columns lane + t*64.
+template <int Q, int T>
+struct PaRowRegs {
+  PaAccVec<T> w0[Q], s1[Q], s2[Q];
+  float a0[Q];
+};
+
+// nontemporal arena traffic: each row is touched exactly once per step and
+// the kernel overlaps the dense graph on another stream — keeping ~0.5
+// GB/step of one-shot data out of L2 leaves it to the GEMMs
+template <int Q, int T>
+__device__ __forceinline__ void pa_load_rows(PaRowRegs<Q, T>& r,
+                                             const PaOptArgs& oa,
+                                             const bool (&ok)[Q],
+                                             float* const (&rows)[Q], int dim,
+                                             int lane) {
+  PaGlobalF* rowk[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) rowk[q] = (PaGlobalF*)rows[q];
+  const bool shared = oa.opt == 1 && pa_adagrad_shared(oa);
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+    r.a0[q] = (shared && ok[q]) ? rowk[q][dim] : 0.0f;
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const int c = lane + t * PA_WAVE;
+    if (c >= dim) continue;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      if (!ok[q]) continue;
+      if (oa.opt != 0 && !shared)
+        r.s1[q][t] = __builtin_nontemporal_load(&rowk[q][dim + c]);
+      if (oa.opt == 2)
+        r.s2[q][t] = __builtin_nontemporal_load(&rowk[q][2 * dim + c]);
+      r.w0[q][t] = __builtin_nontemporal_load(&rowk[q][c]);
+    }
+  }
+}
+
+// Optimizer step of Q loaded rows (pa_load_rows) and their stores.
+template <int Q, int T>
+__device__ __forceinline__ void pa_step_rows(const PaRowRegs<Q, T>& r,
+                                             const PaOptArgs& oa,
+                                             const bool (&ok)[Q],
+                                             float* const (&rows)[Q],
+                                             const PaAccVec<T> (&acc)[Q],
+                                             int dim, int lane) {
+  PaGlobalF* rowk[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) rowk[q] = (PaGlobalF*)rows[q];
+  if (oa.opt == 0) {  // SGD
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int c = lane + t * PA_WAVE;
+      if (c >= dim) continue;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (!ok[q]) continue;
+        __builtin_nontemporal_store(pa_sgd(oa, r.w0[q][t], acc[q][t]),
+                                    &rowk[q][c]);
+      }
+    }
+  } else if (oa.opt == 1) {  // Adagrad
+    if (pa_adagrad_shared(oa)) {
+      float gsq[Q] = {};
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const int c = lane + t * PA_WAVE;
+        if (c >= dim) continue;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          if (!ok[q]) continue;
+          __builtin_nontemporal_store(
+              pa_adagrad_w(oa, r.w0[q][t], r.a0[q], acc[q][t]), &rowk[q][c]);
+          gsq[q] += acc[q][t] * acc[q][t];
+        }
+      }
+#pragma unroll
+      for (int off = PA_WAVE / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) gsq[q] += __shfl_down(gsq[q], off);
+      if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+          if (ok[q])
+            rowk[q][dim] = pa_adagrad_shared_acc(oa, r.a0[q], gsq[q], dim);
+    } else {
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const int c = lane + t * PA_WAVE;
+        if (c >= dim) continue;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          if (!ok[q]) continue;
+          __builtin_nontemporal_store(
+              pa_adagrad_w(oa, r.w0[q][t], r.s1[q][t], acc[q][t]),
+              &rowk[q][c]);
+          __builtin_nontemporal_store(
+              pa_adagrad_acc(oa, r.s1[q][t], acc[q][t]), &rowk[q][dim + c]);
+        }
+      }
+    }
+  } else {  // Adam
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int c = lane + t * PA_WAVE;
+      if (c >= dim) continue;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (!ok[q]) continue;
+        const float m = pa_adam_m(oa, r.s1[q][t], acc[q][t]);
+        const float v = pa_adam_v(oa, r.s2[q][t], acc[q][t]);
+        __builtin_nontemporal_store(pa_adam_w(oa, r.w0[q][t], m, v),
+                                    &rowk[q][c]);
+        __builtin_nontemporal_store(m, &rowk[q][dim + c]);
+        __builtin_nontemporal_store(v, &rowk[q][2 * dim + c]);
+      }
+    }
+  }
+}
+
+// The unhinted form of the same step: per column, load the values of all Q
+// keys, then do the dependent math and store.  Nothing is held across
+// columns, which keeps the kernel without hints at its register budget.
+template <int Q, int T>
+__device__ __forceinline__ void pa_update_rows(const PaOptArgs& oa,
+                                               const bool (&ok)[Q],
+                                               float* const (&rowk)[Q],
+                                               const PaAccVec<T> (&acc)[Q],
+                                               int dim, int lane) {
+  const int opt = oa.opt;
+  // every branch below loads for all Q keys before the dependent math
+  if (opt == 0) {  // SGD
+    for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+      float w0[Q];
+#pragma unroll
+      for (int q = 0; q < Q; ++q)
+        w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (!ok[q]) continue;
+        __builtin_nontemporal_store(pa_sgd(oa, w0[q], acc[q][t]), &rowk[q][c]);
+      }
+    }
+  } else if (opt == 1) {  // Adagrad
+    if (pa_adagrad_shared(oa)) {
+      float a0[Q], gsq[Q] = {};
+#pragma unroll
+      for (int q = 0; q < Q; ++q) a0[q] = ok[q] ? rowk[q][dim] : 0.0f;
+      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+        float w0[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+          w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          if (!ok[q]) continue;
+          __builtin_nontemporal_store(
+              pa_adagrad_w(oa, w0[q], a0[q], acc[q][t]), &rowk[q][c]);
+          gsq[q] += acc[q][t] * acc[q][t];
+        }
+      }
+#pragma unroll
+      for (int off = PA_WAVE / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) gsq[q] += __shfl_down(gsq[q], off);
+      if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+          if (ok[q])
+            rowk[q][dim] = pa_adagrad_shared_acc(oa, a0[q], gsq[q], dim);
+    } else {
+      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+        float w0[Q], a0[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          a0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][dim + c]) : 0.0f;
+          w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          if (!ok[q]) continue;
+          __builtin_nontemporal_store(
+              pa_adagrad_w(oa, w0[q], a0[q], acc[q][t]), &rowk[q][c]);
+          __builtin_nontemporal_store(pa_adagrad_acc(oa, a0[q], acc[q][t]),
+                                      &rowk[q][dim + c]);
+        }
+      }
+    }
+  } else {  // Adam
+    for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (!ok[q]) continue;
+        const float m = pa_adam_m(
+            oa, __builtin_nontemporal_load(&rowk[q][dim + c]), acc[q][t]);
+        const float v = pa_adam_v(
+            oa, __builtin_nontemporal_load(&rowk[q][2 * dim + c]), acc[q][t]);
+        const float w0 = __builtin_nontemporal_load(&rowk[q][c]);
+        __builtin_nontemporal_store(pa_adam_w(oa, w0, m, v), &rowk[q][c]);
+        __builtin_nontemporal_store(m, &rowk[q][dim + c]);
+        __builtin_nontemporal_store(v, &rowk[q][2 * dim + c]);
+      }
+    }
+  }
+}
+
 // Multi-key variant for full-wave dims: one wave updates Q unique keys with
 // interleaved loads — the single-key kernel is latency-bound on its probe ->
 // grads -> arena dependent chain (random 1-2 KB row granules), so Q
@@ -817,10 +1093,19 @@ __global__ void scatter_update_kernel(
 // per key, each lane scans Q/2 of the 32 window slots; after it the whole
 // wave works on every key.  All per-key loops unroll over the constexpr Q so
 // the per-key arrays stay in registers.
-template <int T>
-using PaAccVec = float __attribute__((ext_vector_type(T)));
-
-template <int Q>
+//
+// Update hints (slot_hint/src_hint, both or neither) shorten that chain.
+// The lookup of the same batch already knew each key's slot and, for a key
+// with one position, its gradient row.  A wave whose Q keys all carry
+// in-range hints issues the key verify, the gradient rows, their scales and
+// the arena rows straight off the hints, none waiting on another; it keeps
+// what it loaded only if every table_keys[slot] still holds its key (a later
+// lookup may have evicted the row and reused the slot), and never stores a
+// row it did not verify.  Any other wave takes the probe and the
+// ustarts/perm/seg_id walk below, as every wave does without hints.  The
+// hinted wave is a special case of the all-single branch and computes the
+// same expressions, so the results are the same bits.
+template <int Q, bool HINTS>
 __global__ void scatter_update_multi_kernel(
     ull* __restrict__ table_keys, unsigned* __restrict__ ticks,
     float* __restrict__ arena, const ull* __restrict__ uniq,
@@ -829,7 +1114,9 @@ __global__ void scatter_update_multi_kernel(
     const float* __restrict__ seg_scale, int64_t n, int dim, int row_width,
     int64_t n_buckets, int opt, float p0, float p1, float p2, float p3,
     float b1_power, float b2_power, float weight_bound,
-    int* __restrict__ skipped, const long long* __restrict__ n_dev) {
+    int* __restrict__ skipped, const long long* __restrict__ n_dev,
+    const long long* __restrict__ slot_hint,
+    const long long* __restrict__ src_hint, int64_t n_slots, int64_t n_src) {
   static_assert(Q == 2 || Q == 4, "two or four keys per wave");
   constexpr int WINDOW = PA_PROBE_BUCKETS * PA_BUCKET_SIZE;  // 32
   constexpr int PL = PA_WAVE / Q;   // probe lanes per key
@@ -851,74 +1138,118 @@ __global__ void scatter_update_multi_kernel(
     const int64_t u = w * Q + kq;
     const ull k = (u < n) ? uniq[u] : 0;
     const bool active = (u < n) && (k != PA_EMPTY_KEY);
-    long long slot = -1;
-    if (active) {
-      const int64_t b = (int64_t)(k & (ull)mask);
-#pragma unroll
-      for (int h = 0; h < WS; ++h) {
-        const int wi = widx + h * PL;
-        const int p = wi / PA_BUCKET_SIZE;
-        const int s = wi % PA_BUCKET_SIZE;
-        const int64_t j = ((b + p) & mask) * PA_BUCKET_SIZE + s;
-        if (table_keys[j] == k) slot = j;
-      }
-    }
-    const unsigned long long found = __ballot(slot >= 0);
-    const unsigned long long nonzero = __ballot(k != PA_EMPTY_KEY);
     bool ok[Q];
     float* rowk[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const unsigned fq = (unsigned)((found >> (PL * q)) & PL_MASK);
-      // empty-key (a2a padding) entries skip silently, not as misses
-      ok[q] = (w * Q + q) < n && (nonzero >> (PL * q) & 1ull);
-      if (ok[q] && fq == 0) {
-        if (lane == 0) atomicAdd(&skipped[0], 1);
-        ok[q] = false;
-      }
-      const long long slotq = ok[q] ? __shfl(slot, PL * q + __ffs(fq) - 1) : -1;
-      rowk[q] = ok[q] ? arena + (int64_t)slotq * row_width : nullptr;
-    }
-    // gradient accumulation (whole wave per key; the interleaved
-    // single-position fast path is the overwhelmingly common case)
     // one register vector per key: a [Q][T] array is a single stack object
     // whose runtime column index t costs more registers than Q small ones
     PaAccVec<T> acc[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) acc[q] = 0.0f;
-    int64_t lop[Q], hip[Q];
-    bool all_single = true;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      lop[q] = ok[q] ? ustarts[w * Q + q] : 0;
-      hip[q] = ok[q] ? ustarts[w * Q + q + 1] : 0;
-      all_single = all_single && ok[q] && hip[q] - lop[q] == 1;
-    }
-    if (all_single) {
-      // same rule as pa_reduce_positions: seg_id < 0 or scale 0 leaves the
-      // key's acc at 0 without multiplying its gradient (uniform per key)
-      const __half* gq[Q];
-      float scq[Q];
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const int64_t s = seg_id[perm[lop[q]]];
-        scq[q] = (s >= 0) ? (seg_scale ? seg_scale[s] : 1.0f) : 0.0f;
-        gq[q] = grads + (s >= 0 ? s : 0) * dim;
-      }
-      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+    PaRowRegs<Q, T> rows;  // HINTS only
+    bool hinted = false;
+    if constexpr (HINTS) {
+      const long long sh = active ? slot_hint[u] : -1;
+      const long long sr = active ? src_hint[u] : -1;
+      const bool usable = sh >= 0 && sh < n_slots && sr >= 0 && sr < n_src;
+      if (__ballot(usable) == ~0ull) {
+        const ull kv = table_keys[sh];
+        float scq[Q];
+        __half graw[Q][T];
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-          const float g = __half2float(gq[q][c]);
-          acc[q][t] = (scq[q] != 0.0f) ? scq[q] * g : 0.0f;
+          const long long shq = __shfl(sh, PL * q);
+          const long long srq = __shfl(sr, PL * q);
+          ok[q] = true;
+          rowk[q] = arena + (int64_t)shq * row_width;
+          scq[q] = seg_scale ? seg_scale[srq] : 1.0f;
+          const __half* g = grads + (int64_t)srq * dim;
+#pragma unroll
+          for (int t = 0; t < T; ++t) {
+            const int c = lane + t * PA_WAVE;
+            if (c < dim) graw[q][t] = g[c];
+          }
+        }
+        pa_load_rows<Q, T>(rows, oa, ok, rowk, dim, lane);
+        if (__ballot(kv == k) == ~0ull) {
+          hinted = true;
+          // the all-single expressions below, bit for bit
+#pragma unroll
+          for (int q = 0; q < Q; ++q)
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+              if (lane + t * PA_WAVE < dim)
+                acc[q][t] = (scq[q] != 0.0f)
+                                ? scq[q] * __half2float(graw[q][t])
+                                : 0.0f;
         }
       }
-    } else {
-#pragma unroll
-      for (int q = 0; q < Q; ++q)
-        if (ok[q])
-          pa_reduce_positions<T>(acc[q], grads, perm, seg_id, seg_scale,
-                                 lop[q], hip[q], dim, lane, PA_WAVE);
     }
+    if (!hinted) {
+      long long slot = -1;
+      if (active) {
+        const int64_t b = (int64_t)(k & (ull)mask);
+#pragma unroll
+        for (int h = 0; h < WS; ++h) {
+          const int wi = widx + h * PL;
+          const int p = wi / PA_BUCKET_SIZE;
+          const int s = wi % PA_BUCKET_SIZE;
+          const int64_t j = ((b + p) & mask) * PA_BUCKET_SIZE + s;
+          if (table_keys[j] == k) slot = j;
+        }
+      }
+      const unsigned long long found = __ballot(slot >= 0);
+      const unsigned long long nonzero = __ballot(k != PA_EMPTY_KEY);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const unsigned fq = (unsigned)((found >> (PL * q)) & PL_MASK);
+        // empty-key (a2a padding) entries skip silently, not as misses
+        ok[q] = (w * Q + q) < n && (nonzero >> (PL * q) & 1ull);
+        if (ok[q] && fq == 0) {
+          if (lane == 0) atomicAdd(&skipped[0], 1);
+          ok[q] = false;
+        }
+        const long long slotq =
+            ok[q] ? __shfl(slot, PL * q + __ffs(fq) - 1) : -1;
+        rowk[q] = ok[q] ? arena + (int64_t)slotq * row_width : nullptr;
+      }
+      // gradient accumulation (whole wave per key; the interleaved
+      // single-position fast path is the overwhelmingly common case)
+      int64_t lop[Q], hip[Q];
+      bool all_single = true;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        lop[q] = ok[q] ? ustarts[w * Q + q] : 0;
+        hip[q] = ok[q] ? ustarts[w * Q + q + 1] : 0;
+        all_single = all_single && ok[q] && hip[q] - lop[q] == 1;
+      }
+      if (all_single) {
+        // same rule as pa_reduce_positions: seg_id < 0 or scale 0 leaves the
+        // key's acc at 0 without multiplying its gradient (uniform per key)
+        const __half* gq[Q];
+        float scq[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const int64_t s = seg_id[perm[lop[q]]];
+          scq[q] = (s >= 0) ? (seg_scale ? seg_scale[s] : 1.0f) : 0.0f;
+          gq[q] = grads + (s >= 0 ? s : 0) * dim;
+        }
+        for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+#pragma unroll
+          for (int q = 0; q < Q; ++q) {
+            const float g = __half2float(gq[q][c]);
+            acc[q][t] = (scq[q] != 0.0f) ? scq[q] * g : 0.0f;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+          if (ok[q])
+            pa_reduce_positions<T>(acc[q], grads, perm, seg_id, seg_scale,
+                                   lop[q], hip[q], dim, lane, PA_WAVE);
+      }
+    }
+    // a NaN row is counted and left untouched (a hinted wave drops what it
+    // loaded for it)
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       bool has_nan = false;
@@ -933,79 +1264,12 @@ __global__ void scatter_update_multi_kernel(
 #pragma unroll
     for (int q = 0; q < Q; ++q) any_ok = any_ok || ok[q];
     if (!any_ok) continue;
-    // every branch below loads for all Q keys before the dependent math
-    if (opt == 0) {  // SGD
-      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-        float w0[Q];
-#pragma unroll
-        for (int q = 0; q < Q; ++q)
-          w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          if (!ok[q]) continue;
-          __builtin_nontemporal_store(pa_sgd(oa, w0[q], acc[q][t]), &rowk[q][c]);
-        }
-      }
-    } else if (opt == 1) {  // Adagrad
-      if (pa_adagrad_shared(oa)) {
-        float a0[Q], gsq[Q] = {};
-#pragma unroll
-        for (int q = 0; q < Q; ++q) a0[q] = ok[q] ? rowk[q][dim] : 0.0f;
-        for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-          float w0[Q];
-#pragma unroll
-          for (int q = 0; q < Q; ++q)
-            w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
-#pragma unroll
-          for (int q = 0; q < Q; ++q) {
-            if (!ok[q]) continue;
-            __builtin_nontemporal_store(
-                pa_adagrad_w(oa, w0[q], a0[q], acc[q][t]), &rowk[q][c]);
-            gsq[q] += acc[q][t] * acc[q][t];
-          }
-        }
-#pragma unroll
-        for (int off = PA_WAVE / 2; off > 0; off >>= 1)
-#pragma unroll
-          for (int q = 0; q < Q; ++q) gsq[q] += __shfl_down(gsq[q], off);
-        if (lane == 0)
-#pragma unroll
-          for (int q = 0; q < Q; ++q)
-            if (ok[q])
-              rowk[q][dim] = pa_adagrad_shared_acc(oa, a0[q], gsq[q], dim);
-      } else {
-        for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-          float w0[Q], a0[Q];
-#pragma unroll
-          for (int q = 0; q < Q; ++q) {
-            a0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][dim + c]) : 0.0f;
-            w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
-          }
-#pragma unroll
-          for (int q = 0; q < Q; ++q) {
-            if (!ok[q]) continue;
-            __builtin_nontemporal_store(
-                pa_adagrad_w(oa, w0[q], a0[q], acc[q][t]), &rowk[q][c]);
-            __builtin_nontemporal_store(pa_adagrad_acc(oa, a0[q], acc[q][t]),
-                                        &rowk[q][dim + c]);
-          }
-        }
-      }
-    } else {  // Adam
-      for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          if (!ok[q]) continue;
-          const float m = pa_adam_m(
-              oa, __builtin_nontemporal_load(&rowk[q][dim + c]), acc[q][t]);
-          const float v = pa_adam_v(
-              oa, __builtin_nontemporal_load(&rowk[q][2 * dim + c]), acc[q][t]);
-          const float w0 = __builtin_nontemporal_load(&rowk[q][c]);
-          __builtin_nontemporal_store(pa_adam_w(oa, w0, m, v), &rowk[q][c]);
-          __builtin_nontemporal_store(m, &rowk[q][dim + c]);
-          __builtin_nontemporal_store(v, &rowk[q][2 * dim + c]);
-        }
-      }
+    if constexpr (HINTS) {
+      // the rows of all Q keys are loaded before the dependent math
+      if (!hinted) pa_load_rows<Q, T>(rows, oa, ok, rowk, dim, lane);
+      pa_step_rows<Q, T>(rows, oa, ok, rowk, acc, dim, lane);
+    } else {
+      pa_update_rows<Q, T>(oa, ok, rowk, acc, dim, lane);
     }
   }
 }
@@ -1106,7 +1370,7 @@ void store_lookup(torch::Tensor table_keys, torch::Tensor ticks,
                      spill ? (ull*)evict_keys.data_ptr<int64_t>() : nullptr,
                      spill ? evict_count.data_ptr<int32_t>() : nullptr,
                      spill ? (long long*)evict_idx.data_ptr<int64_t>() : nullptr,
-                     n_dev);
+                     n_dev, nullptr, nullptr, nullptr, nullptr);
   if (out.scalar_type() == torch::kFloat16) {
     // f16 out: distributed wire path (rows go straight onto the a2a)
     hipLaunchKernelGGL(init_gather_kernel<__half>, dim3(n_blocks_for(n, 4)),
@@ -1132,20 +1396,34 @@ void store_lookup(torch::Tensor table_keys, torch::Tensor ticks,
 
 // fast-path lookup: probe/claim + fused init/f16-scatter to sum rows
 // (single-ID groups only — no spill; see init_scatter_kernel)
-void store_lookup_sums(torch::Tensor table_keys, torch::Tensor ticks,
-                       torch::Tensor arena, torch::Tensor query,
-                       torch::Tensor perm, torch::Tensor ustarts,
-                       torch::Tensor sums, int64_t dim, int64_t train,
-                       int64_t tick, double lo, double hi, double admit_prob,
-                       double state_init, int64_t opt_space,
-                       torch::Tensor u_count) {
+//
+// Returns the update hints {slot_hint, src_hint} (nnz-padded i64; entries at
+// or beyond the unique count are unspecified): the slot probe_claim gave each
+// unique key (-1: miss or not admitted) and, when seg_id is given, the
+// gradient row of a key with one position (pa_src_hint).  Without seg_id
+// (eval lookups, hints switched off) no hints are computed and both are empty.
+std::vector<torch::Tensor> store_lookup_sums(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor perm, torch::Tensor ustarts,
+    torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space,
+    torch::Tensor u_count, torch::Tensor seg_id) {
   const int64_t n = query.numel();
-  if (n == 0) return;
+  auto opts = torch::TensorOptions().dtype(torch::kInt64).device(query.device());
+  auto slots = torch::empty({n}, opts);
+  const bool hints = seg_id.numel() > 0;
+  auto src_hint = torch::empty({hints ? n : 0}, opts);
+  if (n == 0) return {src_hint, src_hint};
+  TORCH_CHECK(!hints || seg_id.numel() >= perm.numel(),
+              "store_lookup_sums: seg_id shorter than perm");
+  TORCH_CHECK(!hints || ustarts.numel() > n,
+              "store_lookup_sums: ustarts shorter than query + 1");
+  const int64_t* seg_ptr = hints ? seg_id.data_ptr<int64_t>() : nullptr;
+  long long* src_ptr =
+      hints ? (long long*)src_hint.data_ptr<int64_t>() : nullptr;
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)(dim + opt_space);
   const long long* n_dev = count_or_null(u_count);
-  auto opts = torch::TensorOptions().dtype(torch::kInt64).device(query.device());
-  auto slots = torch::empty({n}, opts);
   auto is_new = torch::empty({n}, opts.dtype(torch::kInt32));
   hipStream_t st = cur_stream();
   hipLaunchKernelGGL(probe_claim_kernel, dim3(n_blocks_for(n, 256)), dim3(256),
@@ -1155,7 +1433,9 @@ void store_lookup_sums(torch::Tensor table_keys, torch::Tensor ticks,
                      (int)train, (unsigned)tick, (float)admit_prob,
                      (long long*)slots.data_ptr<int64_t>(),
                      is_new.data_ptr<int32_t>(), nullptr, nullptr, nullptr,
-                     n_dev);
+                     n_dev, hints ? ustarts.data_ptr<int64_t>() : nullptr,
+                     hints ? perm.data_ptr<int64_t>() : nullptr, seg_ptr,
+                     src_ptr);
   const bool dual = !(dim < PA_WAVE && (PA_WAVE % dim) == 0);
   if (dual) {
     hipLaunchKernelGGL(init_scatter2_kernel,
@@ -1177,6 +1457,8 @@ void store_lookup_sums(torch::Tensor table_keys, torch::Tensor ticks,
                        (__half*)sums.data_ptr<at::Half>(), n, (int)dim,
                        row_width, lo, hi, (float)state_init, n_dev);
   }
+  if (!hints) return {src_hint, src_hint};  // slots was a temporary
+  return {slots, src_hint};
 }
 
 torch::Tensor store_probe(torch::Tensor table_keys, torch::Tensor ticks,
@@ -1197,7 +1479,8 @@ torch::Tensor store_probe(torch::Tensor table_keys, torch::Tensor ticks,
                      /*train=*/0, (unsigned)tick, 1.0f,
                      (long long*)slots.data_ptr<int64_t>(),
                      is_new.data_ptr<int32_t>(), nullptr, nullptr, nullptr,
-                     count_or_null(u_count));
+                     count_or_null(u_count), nullptr, nullptr, nullptr,
+                     nullptr);
   return slots;
 }
 
@@ -1340,11 +1623,30 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
                     torch::Tensor seg_scale, int64_t dim, int64_t opt,
                     std::vector<double> params, double b1_power,
                     double b2_power, double weight_bound,
-                    torch::Tensor skipped, torch::Tensor u_count) {
+                    torch::Tensor skipped, torch::Tensor u_count,
+                    torch::Tensor slot_hint, torch::Tensor src_hint) {
   const int64_t n = uniq.numel();
   if (n == 0) return;
   TORCH_CHECK(grads.scalar_type() == torch::kFloat16, "scatter_update: f16 grads");
   TORCH_CHECK(dim <= 8 * PA_WAVE, "scatter_update: dim too large");
+  // update hints (store_lookup_sums): both or neither, one per entry of uniq
+  const bool hints = slot_hint.numel() > 0;
+  TORCH_CHECK(!hints || (slot_hint.numel() >= n && src_hint.numel() >= n),
+              "scatter_update: hints shorter than uniq");
+  TORCH_CHECK(!hints || (slot_hint.scalar_type() == torch::kInt64 &&
+                         src_hint.scalar_type() == torch::kInt64 &&
+                         slot_hint.device() == uniq.device() &&
+                         src_hint.device() == uniq.device() &&
+                         slot_hint.is_contiguous() && src_hint.is_contiguous()),
+              "scatter_update: hints must be contiguous int64 on uniq's device");
+  // the hinted kernels read seg_scale[src] for any src < grads.size(0)
+  TORCH_CHECK(!hints || seg_scale.numel() == 0 ||
+                  seg_scale.numel() >= grads.size(0),
+              "scatter_update: seg_scale shorter than grads");
+  const long long* slot_ptr =
+      hints ? (const long long*)slot_hint.data_ptr<int64_t>() : nullptr;
+  const long long* src_ptr =
+      hints ? (const long long*)src_hint.data_ptr<int64_t>() : nullptr;
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)arena.size(1);
   // the three variants share one signature: launch `kernel` with one wave
@@ -1363,18 +1665,25 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
                        (float)params[0], (float)params[1], (float)params[2],
                        (float)params[3], (float)b1_power, (float)b2_power,
                        (float)weight_bound, skipped.data_ptr<int32_t>(),
-                       count_or_null(u_count));
+                       count_or_null(u_count), slot_ptr, src_ptr,
+                       table_keys.numel(), grads.size(0));
   };
   // small dividing dims keep the sub-wave-packed kernel (more keys per
   // wave); other dims take as many keys per wave as the register-resident
   // gradient allows (memory-level parallelism), down to one above 256
   const bool packed_small = (dim < PA_WAVE && (PA_WAVE % dim) == 0);
-  if (!packed_small && dim <= 128)
-    launch(scatter_update_multi_kernel<4>, 4);
-  else if (!packed_small && dim <= 256)
-    launch(scatter_update_multi_kernel<2>, 2);
-  else
-    launch(scatter_update_kernel, 1);
+  // the hinted code is a separate instantiation: holding loaded rows across
+  // the verify costs registers, which callers without hints do not pay
+  if (!packed_small && dim <= 128) {
+    if (hints) launch(scatter_update_multi_kernel<4, true>, 4);
+    else launch(scatter_update_multi_kernel<4, false>, 4);
+  } else if (!packed_small && dim <= 256) {
+    if (hints) launch(scatter_update_multi_kernel<2, true>, 2);
+    else launch(scatter_update_multi_kernel<2, false>, 2);
+  } else {
+    if (hints) launch(scatter_update_kernel<true>, 1);
+    else launch(scatter_update_kernel<false>, 1);
+  }
 }
 
 // -> (send [world*cap+1] zero-padded, idx [n_pad]); overflow accumulates
@@ -1486,6 +1795,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("a2a_route", &a2a_route,
         "padded-a2a key routing: range-partition bounds + packed scatter");
   m.def("neq_flags", &neq_flags, "sorted-run boundary flags");
+  namespace py = pybind11;
   m.def("scatter_update", &scatter_update,
-        "fused ordered grad scatter + optimizer update (no [U,dim] buffer)");
+        "fused ordered grad scatter + optimizer update (no [U,dim] buffer); "
+        "slot_hint/src_hint: optional update hints of store_lookup_sums",
+        py::arg("table_keys"), py::arg("ticks"), py::arg("arena"),
+        py::arg("uniq"), py::arg("grads"), py::arg("perm"),
+        py::arg("ustarts"), py::arg("seg_id"), py::arg("seg_scale"),
+        py::arg("dim"), py::arg("opt"), py::arg("params"),
+        py::arg("b1_power"), py::arg("b2_power"), py::arg("weight_bound"),
+        py::arg("skipped"), py::arg("u_count"),
+        py::arg("slot_hint") = torch::empty({0}, torch::kInt64),
+        py::arg("src_hint") = torch::empty({0}, torch::kInt64));
 }

@@ -68,10 +68,18 @@ __device__ __forceinline__ float pa_adagrad_w(const PaOptArgs& a, float w,
   return pa_clamp_weight(a, w - a.p0 * g * rsqrtf(acc + a.p2));
 }
 
-// Adagrad state step, per column
+// Adagrad state step, per column: acc*p1 + g*g as one explicit fma.  Left to
+// the compiler, which of the two products is fused into the add depends on
+// the surrounding kernel, and the choice is part of the result (a last-ulp
+// difference that golden training results and the bit-equality tests between
+// kernels pin).  Default: g*g rounded, acc*p1 fused — what update_kernel and
+// the multi-key kernels compute.  FUSE_GG: acc*p1 rounded, g*g fused — what
+// scatter_update_kernel computes.
+template <bool FUSE_GG = false>
 __device__ __forceinline__ float pa_adagrad_acc(const PaOptArgs& a, float acc,
                                                 float g) {
-  return acc * a.p1 + g * g;
+  if constexpr (FUSE_GG) return __builtin_fmaf(g, g, acc * a.p1);
+  return __builtin_fmaf(acc, a.p1, g * g);
 }
 
 // Adagrad state step, vectorwise-shared: gsq = sum of g*g over the row
