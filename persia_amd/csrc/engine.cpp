@@ -101,8 +101,10 @@ std::vector<torch::Tensor> dedup_padded(torch::Tensor keys) {
   rank.sub_(1);
   auto inverse = torch::empty({nnz}, opts);
   auto uniq = torch::zeros({nnz}, opts);
-  auto ustarts = torch::empty({nnz + 1}, opts);
-  auto u_count = torch::empty({1}, opts);
+  // dedup_finalize launches nothing for an empty input, so the empty result
+  // (no unique keys, ustarts = [0]) is written here
+  auto ustarts = nnz ? torch::empty({nnz + 1}, opts) : torch::zeros({1}, opts);
+  auto u_count = nnz ? torch::empty({1}, opts) : torch::zeros({1}, opts);
   dedup_finalize(svals, perm, neq, rank, /*flip=*/0, inverse, uniq, ustarts,
                  u_count);
   return {uniq, inverse, perm, ustarts, u_count};

@@ -19,6 +19,14 @@
 // CAS on its tick.  Whoever then loses the key CAS or the tick CAS rescans.
 // Table words are read with agent-scope atomic loads so a rescan sees what
 // the peer published.
+//
+// Retries: a lost CAS means a peer took that slot during this launch, and a
+// slot taken during this launch is (once its tick is published) neither empty
+// nor a victim.  So a key loses at most one race per slot of its window
+// before a scan finds nothing to claim: one more attempt than the window has
+// slots.  Fewer would drop keys while the window still has room -- the lanes
+// of a wave that share a window all pick the same first-empty slot, and each
+// retry round admits exactly one of them.
 template <bool kOrdered>
 __device__ __forceinline__ long long probe_claim_impl(
     unsigned long long* __restrict__ keys, unsigned* __restrict__ ticks,
@@ -27,7 +35,8 @@ __device__ __forceinline__ long long probe_claim_impl(
   using ull = unsigned long long;
   const int64_t mask = n_buckets - 1;
   const int64_t b = (int64_t)(k & (ull)mask);
-  for (int attempt = 0; attempt < 16; ++attempt) {
+  constexpr int kAttempts = PA_PROBE_BUCKETS * PA_BUCKET_SIZE + 1;
+  for (int attempt = 0; attempt < kAttempts; ++attempt) {
     long long empty = -1;
     long long victim = -1;
     unsigned victim_tick = 0xFFFFFFFFu;
