@@ -391,8 +391,8 @@ __global__ void update_kernel(ull* __restrict__ table_keys,
       }
     } else {  // Adam
       for (int c = lane; c < dim; c += PA_WAVE) {
-        const float m = pa_adam_m(oa, row[dim + c], g[c]);
-        const float v = pa_adam_v(oa, row[2 * dim + c], g[c]);
+        const float m = pa_adam_m<true>(oa, row[dim + c], g[c]);
+        const float v = pa_adam_v<true>(oa, row[2 * dim + c], g[c]);
         row[c] = pa_adam_w(oa, row[c], m, v);
         row[dim + c] = m;
         row[2 * dim + c] = v;

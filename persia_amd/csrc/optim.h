@@ -6,7 +6,9 @@
 // its own load / compute / store interleaving (the multi-key kernels issue
 // the loads of all their keys before the dependent math).  The expressions
 // are exact-math variants of the reference (persia-simd lib.rs:21-251); every
-// kernel inlines the same expression tree, so they contract identically.
+// kernel inlines the same expression tree.  Where a sum has two products the
+// fused one is written out (pa_adagrad_acc, pa_adam_m, pa_adam_v): which one
+// the compiler contracts is otherwise its choice, per kernel and per column.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -89,12 +91,23 @@ __device__ __forceinline__ float pa_adagrad_shared_acc(const PaOptArgs& a,
   return acc * a.p1 + gsq / (float)dim;
 }
 
-// Adam moment steps, then the weight step from the NEW moments
+// Adam moment steps, then the weight step from the NEW moments.  Both are
+// sums of two products, so as in pa_adagrad_acc the fused product is spelled
+// out: left to the compiler the choice differed between kernels and, inside
+// the hinted multi-key kernels, between unrolled columns, so a hinted update
+// from non-zero moments was not the bits of the unhinted one.  Default: the
+// gradient product fused, the decayed moment rounded — what every fused
+// scatter kernel computed.  FUSE_STATE: the other way round — what
+// update_kernel computed.
+template <bool FUSE_STATE = false>
 __device__ __forceinline__ float pa_adam_m(const PaOptArgs& a, float m, float g) {
-  return a.p1 * m + a.om1 * g;
+  if constexpr (FUSE_STATE) return __builtin_fmaf(a.p1, m, a.om1 * g);
+  return __builtin_fmaf(a.om1, g, a.p1 * m);
 }
+template <bool FUSE_STATE = false>
 __device__ __forceinline__ float pa_adam_v(const PaOptArgs& a, float v, float g) {
-  return a.p2 * v + a.om2 * g * g;
+  if constexpr (FUSE_STATE) return __builtin_fmaf(a.p2, v, a.om2 * g * g);
+  return __builtin_fmaf(a.om2 * g, g, a.p2 * v);
 }
 __device__ __forceinline__ float pa_adam_w(const PaOptArgs& a, float w, float m,
                                            float v) {
