@@ -618,7 +618,8 @@ class EmbeddingEngine:
         idx = torch.where(bad, torch.full_like(pos, dummy), owner * cap + pos)
         send = torch.zeros(dummy + 1, dtype=torch.int64, device=uniq.device)
         send.scatter_(0, idx, uniq)
-        self._a2a_overflow.add_((counts[:world] > cap).sum())
+        # dropped keys, the unit the native route counts in
+        self._a2a_overflow.add_((counts[:world] - cap).clamp(min=0).sum())
         return send, idx
 
     @_roctx_range("persia:a2a_exchange")
@@ -664,9 +665,10 @@ class EmbeddingEngine:
         return rows_full, idx
 
     def check_a2a_overflow(self) -> int:
-        """Batches whose per-owner bucket overflowed `cap` (their keys were
-        dropped to the dummy slot: rows read as zeros, grads discarded).
-        Non-zero means the slack heuristic failed — syncs the device."""
+        """Keys dropped so far because their per-owner bucket was over `cap`
+        (they went to the dummy slot: rows read as zeros, grads discarded);
+        the same unit on the native and the CPU route.  Non-zero means the
+        slack heuristic failed — syncs the device."""
         return int(self._a2a_overflow.sum().item())
 
     # ---------------------------------------------------------- forward path

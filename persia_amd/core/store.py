@@ -718,7 +718,14 @@ class HipEmbeddingStore(EmbeddingStoreBase):
                     wire_dtype: torch.dtype) -> torch.Tensor:
         """Padded-a2a owner lookup: key 0 entries (bucket padding) return
         zeros and never claim slots (kernel-level skip); output is the wire
-        dtype directly (fused f16 cast in init_gather)."""
+        dtype directly (fused f16 cast in init_gather).
+
+        ``keys`` is the receive buffer as it arrives and may repeat a key
+        (once per source rank that asked for it): every occurrence returns the
+        same row, and a key new to the table is claimed once and initialized
+        before any occurrence is read (training runs the init in a launch of
+        its own ahead of the gather; an eval lookup claims nothing and pays
+        nothing for this)."""
         out = torch.empty(
             keys.numel(), self.dim, dtype=wire_dtype, device=self.device
         )

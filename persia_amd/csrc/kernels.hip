@@ -16,7 +16,14 @@
 // slots (one 64B cache line of keys); probe scans 4 consecutive buckets.
 //
 // Concurrency contract (matches the engine's stream discipline):
-//  * keys within one lookup/update call are unique (deduped upstream);
+//  * keys within one lookup/update call are unique (deduped upstream), with
+//    one exception: the wire lookup (store_lookup with f16 rows) takes the
+//    padded all-to-all receive buffer as it arrives, `world` sorted buckets
+//    that repeat a key once per source rank and carry the empty key as
+//    padding.  probe_claim gives every occurrence of a key the same slot and
+//    is_new to exactly one of them; the claimed rows are initialized in a
+//    launch that precedes the gather launch, so every occurrence reads the
+//    initialized row.  The owner-side update dedups the buffer first;
 //  * lookup calls are serialized on one stream (ForwardPipeline);
 //  * an update may overlap a lookup; claims use atomicCAS on the key word,
 //    so the only hazard is an eviction racing an in-flight update of the
@@ -165,11 +172,18 @@ __global__ void probe_claim_kernel(ull* __restrict__ table_keys,
 // one wave per key: init freshly claimed rows, then gather emb -> out.
 // OutT = f32 (local path) or f16 (distributed wire: the gathered rows go
 // straight onto the xGMI all-to-all, so the wire cast is fused here).
+//
+// INIT and GATHER select the two halves.  Unique keys take both in one
+// launch: the wave that initializes a row is the only one that reads it.  A
+// wire buffer repeats keys across its buckets, and only one occurrence of a
+// fresh key is the claimer (is_new), so a training wire lookup runs
+// <INIT, !GATHER> and then <!INIT, GATHER>: the launch boundary orders every
+// init before every read, whichever occurrence claimed.
 __device__ __forceinline__ void pa_store_out(float v, float* p) { *p = v; }
 __device__ __forceinline__ void pa_store_out(float v, __half* p) {
   *p = __float2half(v);
 }
-template <typename OutT>
+template <typename OutT, bool INIT, bool GATHER>
 __global__ void init_gather_kernel(float* __restrict__ arena,
                                    const ull* __restrict__ query,
                                    const long long* __restrict__ slots,
@@ -194,18 +208,21 @@ __global__ void init_gather_kernel(float* __restrict__ arena,
     const long long slot = slots[i];
     OutT* dst = out + i * dim;
     if (slot < 0) {
-      for (int c = c0; c < dim; c += st) pa_store_out(0.0f, dst + c);
+      if (GATHER)
+        for (int c = c0; c < dim; c += st) pa_store_out(0.0f, dst + c);
       continue;
     }
     float* row = arena + (int64_t)slot * row_width;
-    if (evict_rows && is_new[i] && evict_idx[i] >= 0) {
-      // spill: save the victim's full row before overwriting it
-      float* spill = evict_rows + evict_idx[i] * row_width;
-      for (int c = c0; c < row_width; c += st) spill[c] = row[c];
-    }
-    if (is_new[i])
+    if (INIT && is_new[i]) {
+      if (evict_rows && evict_idx[i] >= 0) {
+        // spill: save the victim's full row before overwriting it
+        float* spill = evict_rows + evict_idx[i] * row_width;
+        for (int c = c0; c < row_width; c += st) spill[c] = row[c];
+      }
       pa_init_row(row, query[i], dim, row_width, lo, hi, state_init, c0, st);
-    for (int c = c0; c < dim; c += st) pa_store_out(row[c], dst + c);
+    }
+    if (GATHER)
+      for (int c = c0; c < dim; c += st) pa_store_out(row[c], dst + c);
   }
 }
 
@@ -1371,26 +1388,26 @@ void store_lookup(torch::Tensor table_keys, torch::Tensor ticks,
                      spill ? evict_count.data_ptr<int32_t>() : nullptr,
                      spill ? (long long*)evict_idx.data_ptr<int64_t>() : nullptr,
                      n_dev, nullptr, nullptr, nullptr, nullptr);
-  if (out.scalar_type() == torch::kFloat16) {
-    // f16 out: distributed wire path (rows go straight onto the a2a)
-    hipLaunchKernelGGL(init_gather_kernel<__half>, dim3(n_blocks_for(n, 4)),
-                       dim3(256), 0, st, arena.data_ptr<float>(),
+  auto launch = [&](auto kernel, auto* out_ptr) {
+    hipLaunchKernelGGL(kernel, dim3(n_blocks_for(n, 4)), dim3(256), 0, st,
+                       arena.data_ptr<float>(),
                        (const ull*)query.data_ptr<int64_t>(),
                        (const long long*)slots.data_ptr<int64_t>(),
-                       is_new.data_ptr<int32_t>(),
-                       (__half*)out.data_ptr<at::Half>(), n, (int)dim,
+                       is_new.data_ptr<int32_t>(), out_ptr, n, (int)dim,
                        row_width, lo, hi, (float)state_init,
                        spill ? (const long long*)evict_idx.data_ptr<int64_t>() : nullptr,
                        spill ? evict_rows.data_ptr<float>() : nullptr, n_dev);
+  };
+  if (out.scalar_type() == torch::kFloat16) {
+    // f16 out: distributed wire path (rows go straight onto the a2a).  The
+    // query may repeat a key, so a training lookup initializes every claimed
+    // row in a launch of its own before any row is read (see
+    // init_gather_kernel); an eval lookup claims nothing and only gathers.
+    __half* o = (__half*)out.data_ptr<at::Half>();
+    if (train) launch(init_gather_kernel<__half, true, false>, o);
+    launch(init_gather_kernel<__half, false, true>, o);
   } else {
-    hipLaunchKernelGGL(init_gather_kernel<float>, dim3(n_blocks_for(n, 4)),
-                       dim3(256), 0, st, arena.data_ptr<float>(),
-                       (const ull*)query.data_ptr<int64_t>(),
-                       (const long long*)slots.data_ptr<int64_t>(),
-                       is_new.data_ptr<int32_t>(), out.data_ptr<float>(), n,
-                       (int)dim, row_width, lo, hi, (float)state_init,
-                       spill ? (const long long*)evict_idx.data_ptr<int64_t>() : nullptr,
-                       spill ? evict_rows.data_ptr<float>() : nullptr, n_dev);
+    launch(init_gather_kernel<float, true, true>, out.data_ptr<float>());
   }
 }
 
