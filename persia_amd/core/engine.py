@@ -149,6 +149,51 @@ def _dedup(keys_t: torch.Tensor):
     return uniq, inverse, perm, ustarts
 
 
+def pack_bag_buffer(feats, alloc=None) -> Tuple[np.ndarray, int, int]:
+    """The host staging buffer of a bag group (sum slots with any number of
+    ids per sample), one i64 array
+
+        values[nnz] ‖ slot_starts[S+1] ‖ offsets[S, B+1]
+
+    with each slot's offsets relative to its own start.  -> (buffer, nnz, B).
+    ``alloc(n)`` supplies the writable i64[n] array (pinned memory on the
+    GPU path).
+
+    Each slot's offsets are checked here, once: batches arrive over the byte
+    wire and the device kernels index with these values.  ValueError unless
+    every slot has the same B, and its offsets start at 0, never decrease
+    and end at ``len(values)``."""
+    S = len(feats)
+    B = len(feats[0].offsets) - 1
+    for f in feats:
+        offs = np.asarray(f.offsets)
+        if offs.ndim != 1 or len(offs) - 1 != B or B < 0:
+            raise ValueError(
+                f"slot {f.name}: {len(offs) - 1} samples, the group has {B}"
+            )
+        if offs[0] != 0:
+            raise ValueError(f"slot {f.name}: offsets start at {offs[0]}, not 0")
+        if B and bool((offs[1:] < offs[:-1]).any()):
+            raise ValueError(f"slot {f.name}: offsets decrease")
+        if offs[-1] != len(f.values):
+            raise ValueError(
+                f"slot {f.name}: offsets end at {offs[-1]}, "
+                f"the slot has {len(f.values)} ids"
+            )
+    lens = [len(f.values) for f in feats]
+    nnz = int(sum(lens))
+    total = nnz + (S + 1) + S * (B + 1)
+    buf = np.empty(total, dtype=np.int64) if alloc is None else alloc(total)
+    pos = 0
+    for f, n in zip(feats, lens):
+        buf[pos : pos + n] = np.asarray(f.values, dtype=np.uint64).view(np.int64)
+        pos += n
+    buf[nnz] = 0
+    np.cumsum(lens, out=buf[nnz + 1 : nnz + S + 1])
+    buf[nnz + S + 1 :].reshape(S, B + 1)[:] = [f.offsets for f in feats]
+    return buf, nnz, B
+
+
 @dataclass
 class SlotPayload:
     """What the dense side consumes for one slot (reference
@@ -200,6 +245,11 @@ class _GroupCtx:
     sqrt_mask: Optional[torch.Tensor] = None  # [n_sum_segs] bool
     sum_base: Optional[torch.Tensor] = None  # [n_sum_segs, dim] f16 fused output
     n_sum_slots: int = 0
+    # bag path only: whether a sqrt-scaling slot exists (host bool; None on
+    # the other paths: not known without reading sqrt_mask back) and the
+    # forward's per-segment scale [n_sum_segs] f32, empty = all ones
+    has_sqrt: Optional[bool] = None
+    fwd_scale: Optional[torch.Tensor] = None
     send_counts: Optional[List[int]] = None
     recv_counts: Optional[List[int]] = None
     # capacity-padded even-a2a fast path (sync-free distributed lookup):
@@ -234,6 +284,29 @@ class _GroupPlan:
         self.a2a_ar: Optional[torch.Tensor] = None  # arange(nnz)
         self.a2a_ones: Optional[torch.Tensor] = None  # ones(nnz) count weights
         self.owner_seg_id: Optional[torch.Tensor] = None  # arange(world*cap)
+
+
+class _BagPlan:
+    """Static per-(group, batch-size) device constants of the bag path (sum
+    slots with any number of ids per sample).  The positions vary per batch
+    and come with the upload; only what the slot configs fix lives here."""
+
+    def __init__(self, dim: int, cfgs: List[SlotConfig], B: int,
+                 device: torch.device):
+        self.dim = dim
+        self.B = B
+        self.S = len(cfgs)
+        prefixes_np = np.array([c.index_prefix for c in cfgs], dtype=np.uint64)
+        self.prefixes = torch.from_numpy(prefixes_np.view(np.int64)).to(device)
+        sqrt = [bool(c.sqrt_scaling) for c in cfgs]
+        self.has_sqrt = any(sqrt)
+        # i32[S] for bag_plan; empty = no sqrt slot, no scale tensor at all
+        self.sqrt_flags = torch.tensor(
+            sqrt if self.has_sqrt else [], dtype=torch.int32, device=device
+        )
+        self.sqrt_mask = torch.tensor(
+            sqrt, dtype=torch.bool, device=device
+        ).repeat_interleave(B)
 
 
 class _SplitSlots(torch.autograd.Function):
@@ -336,7 +409,7 @@ class PersiaTrainingBatch:
             a2a_owner = g.a2a_owner_dedup or ()
             for t in (g.uniq_keys, g.inverse, g.perm, g.ustarts, g.u_count,
                       g.slot_hint, g.src_hint, g.sum_base, g.cat_offsets,
-                      g.seg_id, g.seg_lens,
+                      g.seg_id, g.seg_lens, g.fwd_scale,
                       g.sqrt_mask, g.a2a_idx, g.a2a_recv_keys, *a2a_owner):
                 if t is not None and t.is_cuda:
                     yield t
@@ -421,6 +494,10 @@ class EmbeddingEngine:
         # lookup's slot/source hints; 0 asks for and passes none (A/B switch,
         # same results)
         self._update_hints = os.environ.get("PA_UPDATE_HINTS", "1") != "0"
+        # PA_BAG_FAST (default on): single-GPU dim-groups of sum slots with
+        # several ids per sample take the one-call native bag lookup; 0 sends
+        # them down the generic path (A/B switch, same results)
+        self._bag_fast = os.environ.get("PA_BAG_FAST", "1") != "0"
         # PA_ROCTX=1: named roctx ranges around the pipeline stages for
         # rocprofv3 --marker-trace (torch.cuda.nvtx IS roctx on ROCm);
         # off by default so the hot loop never pays the marker calls
@@ -821,8 +898,11 @@ class EmbeddingEngine:
                 if (kind, i) not in pc:
                     pc[(kind, i)] = self._pin_array(x.data)
         for dim, feats in self._feats_by_dim(batch).items():
-            if dim not in pc and self._all_single_sum(feats):
-                pc[dim] = self._pin_values(feats)
+            if self._all_single_sum(feats):
+                if dim not in pc:
+                    pc[dim] = self._pin_values(feats)
+            elif self._bag_group(dim, feats):
+                self._bag_host_buffer(batch, dim, feats)
 
     def _feats_by_dim(self, batch: PersiaBatch) -> Dict[int, List]:
         """A batch's id features by dim-group (one store + one a2a each)."""
@@ -883,6 +963,49 @@ class EmbeddingEngine:
             if not cfg.embedding_summation or cfg.hash_stack_rounds != 0:
                 return False
         return True
+
+    def _bag_group(self, dim: int, feats) -> bool:
+        """The bag-path shape: a single-GPU native group (the one-call
+        condition of _process_group_fast) of sum slots without hashstack, at
+        least one of them with several ids per sample, and PA_BAG_FAST on.
+        All-single-ID groups keep their own path and its static plan."""
+        store = self.stores[dim]
+        if not (
+            self._bag_fast
+            and self.device.type == "cuda"
+            and store.fused_native
+            and not (self.dist.distributed or self._force_dist)
+            and store.spill is None
+        ):
+            return False
+        get_slot = self.schema.get_slot
+        for f in feats:
+            cfg = get_slot(f.name)
+            if not cfg.embedding_summation or cfg.hash_stack_rounds != 0:
+                return False
+        return not all(getattr(f, "is_single", False) for f in feats)
+
+    def _bag_host_buffer(self, batch, dim: int, feats):
+        """A bag group's staging buffer (pack_bag_buffer), built and checked
+        once per (batch, dim-group) and kept in the batch's pinned cache:
+        -> (i64 tensor, nnz, B).  Pinned on the GPU path."""
+        pc = getattr(batch, "_pinned_cache", None)
+        if pc is None:
+            pc = batch._pinned_cache = {}
+        hit = pc.get(("bag", dim))
+        if hit is None:
+            made = []
+
+            def alloc(n: int) -> np.ndarray:
+                made.append(torch.empty(
+                    n, dtype=torch.int64,
+                    pin_memory=self.device.type == "cuda",
+                ))
+                return made[0].numpy()
+
+            _buf, nnz, B = pack_bag_buffer(feats, alloc)
+            hit = pc[("bag", dim)] = (made[0], nnz, B)
+        return hit
 
     def _padded_a2a(self, store) -> bool:
         """Rows travel over the capacity-padded even a2a (not the two-phase
@@ -1005,12 +1128,69 @@ class EmbeddingEngine:
             self._tick("native", t0)
         return group
 
+    def _process_group_bags(self, dim: int, feats, out: PersiaTrainingBatch,
+                            train: bool, batch: PersiaBatch) -> _GroupCtx:
+        """Bag path: sum slots with any number of ids per sample (a single-ID
+        slot is a bag of length 1), single GPU.  One async upload of values
+        and offsets, one native call for sign prep, padded dedup, the segment
+        plan, probe/insert and the sums read straight from the arena.  No
+        host sync between the upload and the return.  The group it leaves is
+        what the generic path leaves, with the unique count on the device."""
+        timing = self._prod_timing
+        if timing:
+            t0 = time.perf_counter()
+        pin, nnz, B = self._bag_host_buffer(batch, dim, feats)
+        names = tuple(f.name for f in feats)
+        plan = self._plans.get(("bag", dim, names, B))
+        if plan is None:
+            plan = self._plans[("bag", dim, names, B)] = _BagPlan(
+                dim, [self.schema.get_slot(n) for n in names], B, self.device
+            )
+        S = plan.S
+        upload = pin.to(self.device, non_blocking=True)
+        if timing:
+            t0 = self._tick("prep", t0)
+        (sums, uniq, inverse, perm, ustarts, u_count, slot_hint, src_hint,
+         cat_offsets, seg_id, seg_lens, fwd_scale) = self.stores[
+            dim
+        ].lookup_local_bags(
+            upload, nnz, S, B, plan.prefixes, self._spacing_arg,
+            plan.sqrt_flags, train and self._update_hints, train,
+        )
+        # per-slot views of the upload: positions on the host, offsets on
+        # the device
+        starts = pin.numpy()[nnz : nnz + S + 1]
+        offsets = upload[nnz + S + 1 :].view(S, B + 1)
+        slot_ctxs = [
+            _SlotCtx(
+                name=f.name, cfg=self.schema.get_slot(f.name),
+                pos_slice=(int(starts[i]), int(starts[i + 1])),
+                seg_offsets=offsets[i], sum_seg_base=i * B,
+            )
+            for i, f in enumerate(feats)
+        ]
+        group = _GroupCtx(
+            dim=dim, uniq_keys=uniq, inverse=inverse, perm=perm,
+            ustarts=ustarts, u_count=u_count, slots=slot_ctxs,
+            cat_offsets=cat_offsets, seg_id=seg_id, seg_lens=seg_lens,
+            sqrt_mask=plan.sqrt_mask, sum_base=sums, n_sum_slots=S,
+            has_sqrt=plan.has_sqrt, fwd_scale=fwd_scale,
+        )
+        if slot_hint.numel():  # both empty when none were asked for
+            group.slot_hint, group.src_hint = slot_hint, src_hint
+        out._lazy_sum_groups.append((group, list(names), B))
+        if timing:
+            self._tick("native", t0)
+        return group
+
     def _process_group(self, dim: int, feats, out: PersiaTrainingBatch, train: bool,
                        batch: PersiaBatch) -> _GroupCtx:
         native = self.device.type == "cuda"
         fast_shape = self._all_single_sum(feats)
         if native and fast_shape:
             return self._process_group_fast(dim, feats, out, train, batch)
+        if self._bag_group(dim, feats):
+            return self._process_group_bags(dim, feats, out, train, batch)
         # sum slots first so they occupy a contiguous prefix of the position
         # space (one fused segment-sum launch for the whole group)
         feats = sorted(
@@ -1208,9 +1388,16 @@ class EmbeddingEngine:
         times the sqrt-scaling factor, zeroed where ``skip`` (bool per
         segment: a NaN slot's segments).  The empty tensor means all ones.
         A ``skip`` caller builds the tensor anyway, so only the others pay
-        the ``any()`` readback that can spare it."""
+        the ``any()`` readback that can spare it; a bag group knows on the
+        host whether it has a sqrt slot and reuses the forward's scale
+        tensor, so it never reads anything back."""
         mask = group.sqrt_mask
-        has_sqrt = mask is not None and (skip is not None or bool(mask.any()))
+        if group.has_sqrt is not None:
+            has_sqrt = group.has_sqrt
+        else:
+            has_sqrt = mask is not None and (
+                skip is not None or bool(mask.any())
+            )
         if skip is None and loss_scale == 1.0 and not has_sqrt:
             return self._empty_scale
         scale = torch.full(
@@ -1218,7 +1405,10 @@ class EmbeddingEngine:
             device=self.device,
         )
         if has_sqrt:
-            scale = scale * _sqrt_scale(mask, group.seg_lens)
+            sqrt_scale = group.fwd_scale
+            if sqrt_scale is None:
+                sqrt_scale = _sqrt_scale(mask, group.seg_lens)
+            scale = scale * sqrt_scale
         if skip is not None:
             scale = torch.where(skip, torch.zeros_like(scale), scale)
         return scale

@@ -171,7 +171,8 @@ class EmbeddingStoreBase:
     """One rank's shard for one dim-group of slots."""
 
     # True where the backend has the fused entry points the engine's
-    # sync-free paths call: lookup_local, update_local, scatter_update
+    # sync-free paths call: lookup_local, lookup_local_bags, update_local,
+    # scatter_update
     fused_native = False
 
     def __init__(
@@ -750,6 +751,25 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         return self._C.lookup_local(
             values, slot_starts, prefixes, spacing_arg, cat_offsets, seg_scale,
             seg_id, self.keys, self.ticks, self.arena,
+            *self._lookup_args(train, self.next_tick()),
+        )
+
+    def lookup_local_bags(self, upload: torch.Tensor, nnz: int, S: int,
+                          B: int, prefixes: torch.Tensor, spacing_arg: int,
+                          sqrt_flags: torch.Tensor, hints: bool, train: bool):
+        """The whole single-GPU lookup of a bag group (sum slots with any
+        number of ids per sample) in one native call.  ``upload`` is the
+        group's device buffer ``values[nnz] ‖ slot_starts[S+1] ‖
+        offsets[S, B+1]`` (engine ``pack_bag_buffer``); ``sqrt_flags`` i32[S]
+        marks the sqrt-scaling slots, empty when there is none.
+        -> (sums, uniq, inverse, perm, ustarts, u_count, slot_hint, src_hint,
+        cat_offsets, seg_id, seg_lens, seg_scale): ``lookup_local``'s results
+        and the group's segment plan.  ``seg_scale`` is empty (all ones)
+        without a sqrt slot; the hints are empty unless ``hints`` and
+        ``train``."""
+        return self._C.lookup_local_bags(
+            upload, nnz, S, B, prefixes, spacing_arg, sqrt_flags, int(hints),
+            self.keys, self.ticks, self.arena,
             *self._lookup_args(train, self.next_tick()),
         )
 

@@ -23,6 +23,15 @@ std::vector<torch::Tensor> store_lookup_sums(
     torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
     double hi, double admit_prob, double state_init, int64_t opt_space,
     torch::Tensor u_count, torch::Tensor seg_id);
+std::vector<torch::Tensor> bag_plan(torch::Tensor plan, int64_t S, int64_t B,
+                                    int64_t nnz, torch::Tensor sqrt_flags);
+std::vector<torch::Tensor> store_lookup_bags(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor inverse, torch::Tensor perm,
+    torch::Tensor ustarts, torch::Tensor cat_offsets, torch::Tensor seg_scale,
+    torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space,
+    torch::Tensor u_count, torch::Tensor seg_id);
 void store_update(torch::Tensor table_keys, torch::Tensor ticks,
                   torch::Tensor arena, torch::Tensor query,
                   torch::Tensor grads, int64_t dim, int64_t opt,
@@ -141,6 +150,60 @@ std::vector<torch::Tensor> lookup_local(
                                  sums, dim, train, tick, lo, hi, admit_prob,
                                  state_init, opt_space, u_count, seg_id);
   return {sums, uniq, inverse, perm, ustarts, u_count, hints[0], hints[1]};
+}
+
+// Single-GPU fused lookup of a bag group: sum slots with any number of ids per
+// sample.  `upload` is the group's one H2D buffer,
+//   values[nnz] ‖ slot_starts[S+1] ‖ offsets[S, B+1]
+// (offsets per slot, relative to the slot's start, checked by the host
+// builder).  sign prep -> padded dedup -> segment plan -> probe/claim -> init
+// launch (training) -> sums straight from the arena.  No host sync, no
+// [U, dim] row buffer.  sqrt_flags i32[S] marks the sqrt-scaling slots, empty
+// when there is none; hints != 0 asks for the update hints (training only).
+// Returns {sums f16 [S*B, dim], uniq, inverse, perm, ustarts, u_count,
+// slot_hint, src_hint, cat_offsets, seg_id, seg_lens, seg_scale}; seg_scale
+// is empty (all ones) without a sqrt slot, the hints are empty unless asked.
+std::vector<torch::Tensor> lookup_local_bags(
+    torch::Tensor upload, int64_t nnz, int64_t S, int64_t B,
+    torch::Tensor prefixes, int64_t spacing, torch::Tensor sqrt_flags,
+    int64_t hints, torch::Tensor table_keys, torch::Tensor ticks,
+    torch::Tensor arena, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space) {
+  TORCH_CHECK(S >= 1 && B >= 0 && nnz >= 0 &&
+                  upload.scalar_type() == torch::kInt64 &&
+                  upload.is_contiguous() &&
+                  upload.numel() == nnz + S + 1 + S * (B + 1),
+              "lookup_local_bags: upload must be i64[nnz + S+1 + S*(B+1)]");
+  TORCH_CHECK(prefixes.numel() == S, "lookup_local_bags: prefixes must be [S]");
+  // sign_prep, the dedup epilogue and probe_claim run one thread per position
+  // on a grid capped at 16384 blocks of 256: beyond that they would leave
+  // positions unwritten
+  TORCH_CHECK(nnz <= (int64_t)16384 * 256,
+              "lookup_local_bags: ", nnz, " ids in one dim-group, the "
+              "thread-per-position kernels cover 4194304");
+  auto values = upload.narrow(0, 0, nnz);
+  auto slot_starts = upload.narrow(0, nnz, S + 1);
+  auto plan = upload.narrow(0, nnz, S + 1 + S * (B + 1));
+  auto keys = sign_prep(values, slot_starts, prefixes, spacing);
+  auto d = dedup_padded(keys);
+  auto& uniq = d[0];
+  auto& inverse = d[1];
+  auto& perm = d[2];
+  auto& ustarts = d[3];
+  auto& u_count = d[4];
+  auto p = bag_plan(plan, S, B, nnz, sqrt_flags);
+  auto& cat_offsets = p[0];
+  auto& seg_id = p[1];
+  auto sums = torch::empty(
+      {S * B, dim},
+      torch::TensorOptions().dtype(torch::kFloat16).device(upload.device()));
+  const bool want_hints = train && hints;
+  auto h = store_lookup_bags(
+      table_keys, ticks, arena, uniq, inverse, perm, ustarts, cat_offsets,
+      p[3], sums, dim, train, tick, lo, hi, admit_prob, state_init, opt_space,
+      u_count, want_hints ? seg_id : seg_id.narrow(0, 0, 0));
+  return {sums,       uniq, inverse,     perm,   ustarts, u_count,
+          h[0],       h[1], cat_offsets, seg_id, p[2],    p[3]};
 }
 
 // Single-GPU fused backward: per-segment grads -> per-sign scatter -> fused
@@ -322,6 +385,9 @@ void init_engine(pybind11::module_& m) {
       .def("clear", &NativeHostTier::clear);
   m.def("lookup_local", &lookup_local,
         "fused single-GPU lookup (sign prep + dedup + probe + gather + sum)");
+  m.def("lookup_local_bags", &lookup_local_bags,
+        "fused single-GPU lookup of a multi-ID sum group (sign prep + dedup + "
+        "segment plan + probe + init + sums from the arena)");
   m.def("update_local", &update_local,
         "fused single-GPU backward (scatter + optimizer update)");
 }

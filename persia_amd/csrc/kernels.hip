@@ -662,6 +662,138 @@ __global__ void segment_sum_kernel(const RowT* __restrict__ rows,
   }
 }
 
+// ------------------------------------------------ bag (multi-ID) sum lookup
+
+// Segment plan of a bag group, from the uploaded per-slot CSR.  `plan` is
+// slot_starts[S+1] followed by offsets[S, B+1] (each slot's offsets relative
+// to its start; the host builder has checked them: first 0, non-decreasing,
+// last == the slot's length).  Segment s*B+b is sample b of slot s.
+//   cat_offsets[s*B+b] = slot_starts[s] + offsets[s][b],  cat_offsets[S*B] = nnz
+//   seg_id[p]          = segment of position p
+//   seg_lens[seg]      = (float)len
+//   seg_scale[seg]     = sqrt slot ? rsqrtf(max(len, 1)) : 1   (optional)
+// Thread i serves segment i and position i.  A position finds its slot and
+// sample by binary search (the last start <= p: empty slots and empty bags
+// repeat a start, and the position belongs behind them).
+__global__ void bag_plan_kernel(const int64_t* __restrict__ plan,
+                                const int* __restrict__ sqrt_flags, int S,
+                                int64_t B, int64_t nnz,
+                                int64_t* __restrict__ cat_offsets,
+                                int64_t* __restrict__ seg_id,
+                                float* __restrict__ seg_lens,
+                                float* __restrict__ seg_scale) {
+  const int64_t n_seg = (int64_t)S * B;
+  const int64_t n = n_seg + 1 > nnz ? n_seg + 1 : nnz;
+  const int64_t* slot_starts = plan;
+  const int64_t* offsets = plan + S + 1;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < n_seg) {
+      const int64_t s = i / B, b = i % B;
+      const int64_t* off = offsets + s * (B + 1);
+      const int64_t len = off[b + 1] - off[b];
+      cat_offsets[i] = slot_starts[s] + off[b];
+      seg_lens[i] = (float)len;
+      if (seg_scale)
+        seg_scale[i] =
+            sqrt_flags[s] ? rsqrtf(fmaxf((float)len, 1.0f)) : 1.0f;
+    } else if (i == n_seg) {
+      cat_offsets[i] = nnz;
+    }
+    if (i < nnz) {
+      int lo = 0, hi = S;  // slot_starts[lo] <= i < slot_starts[lo + 1]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (i >= slot_starts[mid]) lo = mid; else hi = mid;
+      }
+      const int64_t* off = offsets + (int64_t)lo * (B + 1);
+      const int64_t q = i - slot_starts[lo];
+      int64_t blo = 0, bhi = B;  // off[blo] <= q < off[blo + 1]
+      while (bhi - blo > 1) {
+        const int64_t mid = (blo + bhi) >> 1;
+        if (q >= off[mid]) blo = mid; else bhi = mid;
+      }
+      seg_id[i] = (int64_t)lo * B + blo;
+    }
+  }
+}
+
+// out[s, c] = f16( (sum_{k in [off[s], off[s+1])} row(k)[c]) * scale[s] ),
+// row(k) = arena[slots[inverse[k]]]; a slot < 0 (miss, not admitted) adds
+// nothing.  segment_sum_kernel reading the arena: same lane layout, and the
+// adds run in position order in f32 from +0, so the bits equal a gather into
+// a [U, dim] buffer followed by segment_sum (a skipped row is that path's
+// +0 row: the accumulator is never -0, so adding +0 leaves it).
+//
+// inverse -> slots -> arena row is three dependent loads per addend on random
+// row granules (the latency chain of scatter_update_multi_kernel and
+// init_scatter2_kernel).  Addends go in groups of PA_BAG_DEPTH: all index
+// loads, then all slot loads, then all row loads are issued before the first
+// add.  Every load of a group is unconditional (a position past the bag's
+// end re-reads the bag's last one, a missing row reads row 0, and the value
+// is replaced by +0 afterwards), so no branch separates the loads and the
+// compiler keeps them in flight together.  A lane holds T columns
+// (c0 + t*st) of the row per pass; dims above T*64 take further passes.
+#define PA_BAG_DEPTH 4
+template <int T>
+__global__ void bag_sum_kernel(const float* __restrict__ arena,
+                               const long long* __restrict__ slots,
+                               const int64_t* __restrict__ inverse,
+                               const int64_t* __restrict__ seg_offsets,
+                               const float* __restrict__ seg_scale,
+                               __half* __restrict__ out, int64_t n_seg,
+                               int dim, int row_width) {
+  const int wave = threadIdx.x / PA_WAVE;
+  const int lane = threadIdx.x % PA_WAVE;
+  const int waves_per_block = blockDim.x / PA_WAVE;
+  const PaLanes L = pa_lanes(lane, dim);
+  const int64_t n_waveitems = (n_seg + L.G - 1) / L.G;
+  for (int64_t w = (int64_t)blockIdx.x * waves_per_block + wave;
+       w < n_waveitems; w += (int64_t)gridDim.x * waves_per_block) {
+    const int64_t s = w * L.G + L.sub;
+    if (s >= n_seg) continue;
+    const int64_t lo = seg_offsets[s], hi = seg_offsets[s + 1];
+    const float scale = seg_scale ? seg_scale[s] : 1.0f;
+    __half* dst = out + s * dim;
+    for (int cb = L.c0; cb < dim; cb += T * L.st) {
+      int col[T];  // a column past dim re-reads cb; it is never stored
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        col[t] = (cb + t * L.st < dim) ? cb + t * L.st : cb;
+      float acc[T];
+#pragma unroll
+      for (int t = 0; t < T; ++t) acc[t] = 0.0f;
+      for (int64_t k = lo; k < hi; k += PA_BAG_DEPTH) {
+        int64_t u[PA_BAG_DEPTH];
+        long long sl[PA_BAG_DEPTH];
+        float v[PA_BAG_DEPTH][T];
+#pragma unroll
+        for (int j = 0; j < PA_BAG_DEPTH; ++j)
+          u[j] = inverse[(k + j < hi) ? k + j : hi - 1];
+#pragma unroll
+        for (int j = 0; j < PA_BAG_DEPTH; ++j) sl[j] = slots[u[j]];
+#pragma unroll
+        for (int j = 0; j < PA_BAG_DEPTH; ++j) {
+          const float* row =
+              arena + (int64_t)(sl[j] >= 0 ? sl[j] : 0) * row_width;
+#pragma unroll
+          for (int t = 0; t < T; ++t) v[j][t] = row[col[t]];
+        }
+#pragma unroll
+        for (int j = 0; j < PA_BAG_DEPTH; ++j) {
+          const bool live = (k + j < hi) && sl[j] >= 0;
+#pragma unroll
+          for (int t = 0; t < T; ++t) acc[t] += live ? v[j][t] : 0.0f;
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        if (cb + t * L.st < dim)
+          dst[cb + t * L.st] = __float2half(acc[t] * scale);
+    }
+  }
+}
+
 // --------------------------------------------------- ordered gradient scatter
 
 // out[u, :] += sum_{p in [ustart[u], ustart[u+1])} grads[seg_id[perm[p]], :]
@@ -1478,6 +1610,118 @@ std::vector<torch::Tensor> store_lookup_sums(
   return {slots, src_hint};
 }
 
+// Segment plan of a bag group (bag_plan_kernel).  `plan` is the uploaded
+// slot_starts[S+1] ‖ offsets[S, B+1]; sqrt_flags i32[S] marks the sqrt-scaling
+// slots and is empty when the group has none.
+// -> {cat_offsets i64[S*B+1], seg_id i64[nnz], seg_lens f32[S*B],
+//     seg_scale f32[S*B], or empty (all ones) without a sqrt slot}
+std::vector<torch::Tensor> bag_plan(torch::Tensor plan, int64_t S, int64_t B,
+                                    int64_t nnz, torch::Tensor sqrt_flags) {
+  TORCH_CHECK(S >= 1 && B >= 0 && nnz >= 0, "bag_plan: bad shape");
+  TORCH_CHECK(plan.scalar_type() == torch::kInt64 && plan.is_contiguous() &&
+                  plan.numel() == S + 1 + S * (B + 1),
+              "bag_plan: plan must be i64[S+1 + S*(B+1)]");
+  const bool scaled = sqrt_flags.numel() > 0;
+  TORCH_CHECK(!scaled || (sqrt_flags.scalar_type() == torch::kInt32 &&
+                          sqrt_flags.numel() == S),
+              "bag_plan: sqrt_flags must be i32[S]");
+  auto opts = torch::TensorOptions().dtype(torch::kInt64).device(plan.device());
+  const int64_t n_seg = S * B;
+  auto cat_offsets = torch::empty({n_seg + 1}, opts);
+  auto seg_id = torch::empty({nnz}, opts);
+  auto seg_lens = torch::empty({n_seg}, opts.dtype(torch::kFloat32));
+  auto seg_scale =
+      torch::empty({scaled ? n_seg : 0}, opts.dtype(torch::kFloat32));
+  const int64_t n = std::max(n_seg + 1, nnz);  // >= 1: no empty launch
+  hipLaunchKernelGGL(bag_plan_kernel, dim3(n_blocks_for(n, 256)), dim3(256), 0,
+                     cur_stream(), plan.data_ptr<int64_t>(),
+                     scaled ? sqrt_flags.data_ptr<int32_t>() : nullptr, (int)S,
+                     B, nnz, cat_offsets.data_ptr<int64_t>(),
+                     seg_id.data_ptr<int64_t>(), seg_lens.data_ptr<float>(),
+                     scaled ? seg_scale.data_ptr<float>() : nullptr);
+  return {cat_offsets, seg_id, seg_lens, seg_scale};
+}
+
+// Bag lookup over the unique keys of a dedup: probe/claim, a launch that only
+// initializes the freshly claimed rows (training), then the segment sums read
+// straight from the arena (bag_sum_kernel) — no [U, dim] row buffer.  The
+// init launch precedes the sum launch because a fresh row is read by every
+// segment that holds its key, not by the wave that claimed it.
+// Returns the update hints {slot_hint, src_hint} as store_lookup_sums does:
+// both empty unless seg_id is given.
+std::vector<torch::Tensor> store_lookup_bags(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor inverse, torch::Tensor perm,
+    torch::Tensor ustarts, torch::Tensor cat_offsets, torch::Tensor seg_scale,
+    torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space,
+    torch::Tensor u_count, torch::Tensor seg_id) {
+  const int64_t n = query.numel();
+  const int64_t n_seg = cat_offsets.numel() - 1;
+  auto opts = torch::TensorOptions().dtype(torch::kInt64).device(query.device());
+  const bool hints = seg_id.numel() > 0;
+  auto src_hint = torch::empty({hints ? n : 0}, opts);
+  TORCH_CHECK(inverse.numel() == n && perm.numel() == n && ustarts.numel() > n,
+              "store_lookup_bags: dedup tensors do not match the query");
+  TORCH_CHECK(sums.size(0) == n_seg && sums.size(1) == dim &&
+                  sums.is_contiguous(),
+              "store_lookup_bags: sums must be [n_seg, dim]");
+  TORCH_CHECK(!seg_scale.numel() || seg_scale.numel() == n_seg,
+              "store_lookup_bags: seg_scale must be empty or [n_seg]");
+  TORCH_CHECK(!hints || seg_id.numel() >= n,
+              "store_lookup_bags: seg_id shorter than perm");
+  if (n == 0) {  // every bag empty: nothing to probe, the sums are zeros
+    sums.zero_();
+    return {src_hint, src_hint};
+  }
+  auto slots = torch::empty({n}, opts);
+  auto is_new = torch::empty({n}, opts.dtype(torch::kInt32));
+  const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
+  const int row_width = (int)(dim + opt_space);
+  const long long* n_dev = count_or_null(u_count);
+  hipStream_t st = cur_stream();
+  hipLaunchKernelGGL(probe_claim_kernel, dim3(n_blocks_for(n, 256)), dim3(256),
+                     0, st, (ull*)table_keys.data_ptr<int64_t>(),
+                     (unsigned*)ticks.data_ptr<int32_t>(),
+                     (const ull*)query.data_ptr<int64_t>(), n, n_buckets,
+                     (int)train, (unsigned)tick, (float)admit_prob,
+                     (long long*)slots.data_ptr<int64_t>(),
+                     is_new.data_ptr<int32_t>(), nullptr, nullptr, nullptr,
+                     n_dev, hints ? ustarts.data_ptr<int64_t>() : nullptr,
+                     hints ? perm.data_ptr<int64_t>() : nullptr,
+                     hints ? seg_id.data_ptr<int64_t>() : nullptr,
+                     hints ? (long long*)src_hint.data_ptr<int64_t>() : nullptr);
+  if (train)  // an eval lookup claims nothing: nothing to initialize
+    hipLaunchKernelGGL((init_gather_kernel<float, true, false>),
+                       dim3(n_blocks_for(n, 4)), dim3(256), 0, st,
+                       arena.data_ptr<float>(),
+                       (const ull*)query.data_ptr<int64_t>(),
+                       (const long long*)slots.data_ptr<int64_t>(),
+                       is_new.data_ptr<int32_t>(), (float*)nullptr, n,
+                       (int)dim, row_width, lo, hi, (float)state_init, nullptr,
+                       nullptr, n_dev);
+  if (n_seg > 0) {
+    const dim3 grid(n_blocks_for(n_seg, 4)), block(256);
+    const bool packed = dim < PA_WAVE && (PA_WAVE % dim) == 0;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, st, arena.data_ptr<float>(),
+                         (const long long*)slots.data_ptr<int64_t>(),
+                         inverse.data_ptr<int64_t>(),
+                         cat_offsets.data_ptr<int64_t>(),
+                         scale_or_null(seg_scale),
+                         (__half*)sums.data_ptr<at::Half>(), n_seg, (int)dim,
+                         row_width);
+    };
+    // columns a lane holds per pass: the whole row up to dim 512
+    if (packed || dim <= PA_WAVE) launch(bag_sum_kernel<1>);
+    else if (dim <= 2 * PA_WAVE) launch(bag_sum_kernel<2>);
+    else if (dim <= 4 * PA_WAVE) launch(bag_sum_kernel<4>);
+    else launch(bag_sum_kernel<8>);
+  }
+  if (!hints) return {src_hint, src_hint};  // slots was a temporary
+  return {slots, src_hint};
+}
+
 torch::Tensor store_probe(torch::Tensor table_keys, torch::Tensor ticks,
                           torch::Tensor query, int64_t tick,
                           torch::Tensor u_count) {
@@ -1797,6 +2041,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("store_probe", &store_probe, "probe-only (spill-tier miss detection)");
   m.def("store_lookup_sums", &store_lookup_sums,
         "fast-path lookup: probe + fused init/f16 scatter to sum rows");
+  m.def("bag_plan", &bag_plan,
+        "bag group segment plan from the uploaded per-slot CSR");
+  m.def("store_lookup_bags", &store_lookup_bags,
+        "bag lookup: probe + init launch + segment sums read from the arena");
   m.def("store_update", &store_update, "fused sparse optimizer update");
   m.def("store_import", &store_import, "bulk insert rows (checkpoint load)");
   m.def("segment_sum", &segment_sum, "fused gather + per-sample summation");
