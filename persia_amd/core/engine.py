@@ -194,10 +194,26 @@ def pack_bag_buffer(feats, alloc=None) -> Tuple[np.ndarray, int, int]:
     return buf, nnz, B
 
 
+def raw_slot_meta(S: int, B: int, sfs: List[int]) -> np.ndarray:
+    """Where the raw slots of a raw-path group sit in its leaf base, as the
+    native lookup takes it: i64 ``row_base[R] ‖ sfs[R]``.  The base holds the
+    S*B sum segments first, then per raw slot its B*sfs cell rows
+    (sample-major), so ``row_base[r] = S*B + sum_{r' < r} B*sfs[r']``."""
+    bases = S * B + B * np.concatenate([[0], np.cumsum(sfs[:-1])])
+    return np.concatenate([bases, sfs]).astype(np.int64)
+
+
 @dataclass
 class SlotPayload:
     """What the dense side consumes for one slot (reference
-    FeatureEmbeddingBatch, persia-common/src/lib.rs:85-113)."""
+    FeatureEmbeddingBatch, persia-common/src/lib.rs:85-113).
+
+    A raw slot comes under one of two contracts.  The generic path fills
+    ``raw_distinct`` / ``raw_index`` / ``raw_non_empty_index`` (the
+    reference's distinct rows and index tensors; the consumer index-selects).
+    The native raw path fills ``raw_rows`` / ``raw_mask`` instead, the
+    fixed-size tensor itself, and leaves those three ``None``: it never builds
+    per-slot distinct rows."""
 
     name: str
     cfg: SlotConfig
@@ -205,11 +221,14 @@ class SlotPayload:
     raw_distinct: Optional[torch.Tensor] = None  # [U_slot+1, dim] f16, row0 pad
     raw_index: Optional[torch.Tensor] = None  # [B*sfs] i64
     raw_non_empty_index: Optional[torch.Tensor] = None
-    raw_sample_id_num: Optional[torch.Tensor] = None
+    raw_sample_id_num: Optional[torch.Tensor] = None  # [B] i64 min(len, sfs)
+    # native raw path: views of the group's leaf base and mask
+    raw_rows: Optional[torch.Tensor] = None  # [B, sfs, dim] f16
+    raw_mask: Optional[torch.Tensor] = None  # [B, sfs, 1] f16, 1 = holds an id
 
     @property
     def is_raw(self) -> bool:
-        return self.raw_distinct is not None
+        return self.raw_distinct is not None or self.raw_rows is not None
 
 
 @dataclass
@@ -221,6 +240,10 @@ class _SlotCtx:
     sum_seg_base: int = -1  # sum slots: base index in the group segment space
     slot_uniq_global: Optional[torch.Tensor] = None  # raw slots: local->global uniq
     slot_inverse: Optional[torch.Tensor] = None  # raw slots: pos->local distinct
+    # native raw path: the slot's B*raw_sfs cell rows start at raw_row_base of
+    # the group's leaf base (raw_sfs 0: not a raw-path slot)
+    raw_row_base: int = -1
+    raw_sfs: int = 0
 
 
 @dataclass
@@ -250,6 +273,11 @@ class _GroupCtx:
     # forward's per-segment scale [n_sum_segs] f32, empty = all ones
     has_sqrt: Optional[bool] = None
     fwd_scale: Optional[torch.Tensor] = None
+    # native raw path only: sum_base is the whole leaf base, the n_sum_slots
+    # sum slots' segments first, then every raw slot's cell rows; seg_id sends
+    # a raw position to its cell row and fwd_scale (if any) covers all rows
+    raw_mask: Optional[torch.Tensor] = None  # [base rows - n_sum_segs] f16
+    raw_num: Optional[torch.Tensor] = None  # [R*B] i64 min(len, sfs)
     send_counts: Optional[List[int]] = None
     recv_counts: Optional[List[int]] = None
     # capacity-padded even-a2a fast path (sync-free distributed lookup):
@@ -309,26 +337,70 @@ class _BagPlan:
         ).repeat_interleave(B)
 
 
+class _RawPlan:
+    """Static per-(group, batch-size) constants of the native raw path: S sum
+    slots, then R raw slots (``cfgs`` in that order).  Prefixes of all slots,
+    sqrt flags of the sum slots, and per raw slot its ``sample_fixed_size``
+    and the first row of its cells in the leaf base (raw_slot_meta)."""
+
+    def __init__(self, dim: int, cfgs: List[SlotConfig], B: int,
+                 device: torch.device):
+        self.dim = dim
+        self.B = B
+        sums = [c for c in cfgs if c.embedding_summation]
+        self.S = S = len(sums)
+        prefixes_np = np.array([c.index_prefix for c in cfgs], dtype=np.uint64)
+        self.prefixes = torch.from_numpy(prefixes_np.view(np.int64)).to(device)
+        sqrt = [bool(c.sqrt_scaling) for c in sums]
+        self.has_sqrt = any(sqrt)
+        self.sqrt_flags = torch.tensor(
+            sqrt if self.has_sqrt else [], dtype=torch.int32, device=device
+        )
+        self.sqrt_mask = torch.tensor(
+            sqrt, dtype=torch.bool, device=device
+        ).repeat_interleave(B)
+        self.sfs = [int(c.sample_fixed_size) for c in cfgs[S:]]
+        meta = raw_slot_meta(S, B, self.sfs)
+        self.row_bases = [int(x) for x in meta[: len(self.sfs)]]
+        self.raw_meta = torch.from_numpy(meta).to(device)
+
+
 class _SplitSlots(torch.autograd.Function):
     """Split a group's fused sum tensor into per-slot views with ONE backward
     op: autograd's native per-view SliceBackward would zero-fill and add a
-    full-base-sized buffer per slot (2×n_slots kernels per step)."""
+    full-base-sized buffer per slot (2×n_slots kernels per step).  ``rows``
+    is each slot's row count: B for a sum slot, B*sfs for a raw-path slot."""
 
     @staticmethod
-    def forward(ctx, base: torch.Tensor, n_slots: int, B: int):
-        ctx.n_slots, ctx.B, ctx.dim = n_slots, B, base.shape[1]
+    def forward(ctx, base: torch.Tensor, rows: Tuple[int, ...]):
+        ctx.rows, ctx.dim = rows, base.shape[1]
         ctx.dev, ctx.dtype = base.device, base.dtype
-        return tuple(base[i * B : (i + 1) * B] for i in range(n_slots))
+        return base.split(list(rows), dim=0)
 
     @staticmethod
     def backward(ctx, *grads):
         parts = [
             g
             if g is not None
-            else torch.zeros(ctx.B, ctx.dim, dtype=ctx.dtype, device=ctx.dev)
-            for g in grads
+            else torch.zeros(n, ctx.dim, dtype=ctx.dtype, device=ctx.dev)
+            for g, n in zip(grads, ctx.rows)
         ]
-        return torch.cat(parts, dim=0), None, None
+        return torch.cat(parts, dim=0), None
+
+
+def _raw_path_payload(group: _GroupCtx, r: int, B: int) -> SlotPayload:
+    """The payload of raw slot r of a raw-path group: views of the group's
+    leaf base and mask."""
+    sc = group.slots[group.n_sum_slots + r]
+    n, dim = B * sc.raw_sfs, group.dim
+    r0 = sc.raw_row_base
+    m0 = r0 - group.n_sum_slots * B
+    return SlotPayload(
+        name=sc.name, cfg=sc.cfg,
+        raw_rows=group.sum_base[r0 : r0 + n].view(B, sc.raw_sfs, dim),
+        raw_mask=group.raw_mask[m0 : m0 + n].view(B, sc.raw_sfs, 1),
+        raw_sample_id_num=group.raw_num[r * B : (r + 1) * B],
+    )
 
 
 class PersiaTrainingBatch:
@@ -362,6 +434,11 @@ class PersiaTrainingBatch:
             for group, _names, B in self._lazy_sum_groups:
                 sums = group.sum_base
                 for i, sc in enumerate(group.slots):
+                    if sc.raw_sfs:
+                        self._payloads.append(
+                            _raw_path_payload(group, i - group.n_sum_slots, B)
+                        )
+                        continue
                     self._payloads.append(
                         SlotPayload(name=sc.name, cfg=sc.cfg,
                                     sum_tensor=sums[i * B : (i + 1) * B])
@@ -377,15 +454,26 @@ class PersiaTrainingBatch:
     def enable_training_views(self) -> Dict[str, torch.Tensor]:
         """Mark each group's sum base requires_grad and return fresh per-slot
         views connected to it (autograd accumulates into ``sum_base.grad`` —
-        consumed by ``EmbeddingEngine.apply_gradients_base``)."""
+        consumed by ``EmbeddingEngine.apply_gradients_base``).  A raw-path
+        slot's view is its ``(B, sfs, dim)`` rows, off the same backward
+        node."""
         views: Dict[str, torch.Tensor] = {}
+        B = self.batch_size
         for group in self._groups:
             if group.sum_base is None:
                 continue
             group.sum_base.requires_grad_(True)
-            sum_names = [sc.name for sc in group.slots if sc.cfg.embedding_summation]
-            parts = _SplitSlots.apply(group.sum_base, len(sum_names), self.batch_size)
-            views.update(zip(sum_names, parts))
+            in_base = [
+                sc for sc in group.slots
+                if sc.cfg.embedding_summation or sc.raw_sfs
+            ]
+            parts = _SplitSlots.apply(
+                group.sum_base, tuple(B * (sc.raw_sfs or 1) for sc in in_base)
+            )
+            for sc, part in zip(in_base, parts):
+                if sc.raw_sfs:
+                    part = part.view(B, sc.raw_sfs, group.dim)
+                views[sc.name] = part
         return views
 
     def training_embeddings(self) -> List[torch.Tensor]:
@@ -409,7 +497,7 @@ class PersiaTrainingBatch:
             a2a_owner = g.a2a_owner_dedup or ()
             for t in (g.uniq_keys, g.inverse, g.perm, g.ustarts, g.u_count,
                       g.slot_hint, g.src_hint, g.sum_base, g.cat_offsets,
-                      g.seg_id, g.seg_lens, g.fwd_scale,
+                      g.seg_id, g.seg_lens, g.fwd_scale, g.raw_mask, g.raw_num,
                       g.sqrt_mask, g.a2a_idx, g.a2a_recv_keys, *a2a_owner):
                 if t is not None and t.is_cuda:
                     yield t
@@ -417,9 +505,9 @@ class PersiaTrainingBatch:
                 for t in (sc.seg_offsets, sc.slot_uniq_global, sc.slot_inverse):
                     if t is not None and t.is_cuda:
                         yield t
-        # lazy groups hold only sum payloads (no per-payload device tensors),
-        # so iterating the eagerly-built list is sufficient and avoids
-        # materializing payloads in the pipeline thread
+        # lazy groups hold only payloads that are views of group tensors (no
+        # per-payload device tensors), so iterating the eagerly-built list is
+        # sufficient and avoids materializing payloads in the pipeline thread
         for p in self._payloads:
             for t in (p.raw_distinct, p.raw_index, p.raw_non_empty_index,
                       p.raw_sample_id_num):
@@ -498,6 +586,10 @@ class EmbeddingEngine:
         # several ids per sample take the one-call native bag lookup; 0 sends
         # them down the generic path (A/B switch, same results)
         self._bag_fast = os.environ.get("PA_BAG_FAST", "1") != "0"
+        # PA_RAW_FAST (default on): single-GPU dim-groups with raw (sequence)
+        # slots and no hashstack take the one-call native raw lookup; 0 sends
+        # them down the generic path (A/B switch)
+        self._raw_fast = os.environ.get("PA_RAW_FAST", "1") != "0"
         # PA_ROCTX=1: named roctx ranges around the pipeline stages for
         # rocprofv3 --marker-trace (torch.cuda.nvtx IS roctx on ROCm);
         # off by default so the hot loop never pays the marker calls
@@ -903,6 +995,10 @@ class EmbeddingEngine:
                     pc[dim] = self._pin_values(feats)
             elif self._bag_group(dim, feats):
                 self._bag_host_buffer(batch, dim, feats)
+            elif self._raw_group(dim, feats):
+                self._bag_host_buffer(
+                    batch, dim, self._sums_first(feats), kind="raw"
+                )
 
     def _feats_by_dim(self, batch: PersiaBatch) -> Dict[int, List]:
         """A batch's id features by dim-group (one store + one a2a each)."""
@@ -969,14 +1065,7 @@ class EmbeddingEngine:
         condition of _process_group_fast) of sum slots without hashstack, at
         least one of them with several ids per sample, and PA_BAG_FAST on.
         All-single-ID groups keep their own path and its static plan."""
-        store = self.stores[dim]
-        if not (
-            self._bag_fast
-            and self.device.type == "cuda"
-            and store.fused_native
-            and not (self.dist.distributed or self._force_dist)
-            and store.spill is None
-        ):
+        if not (self._bag_fast and self._one_call(dim)):
             return False
         get_slot = self.schema.get_slot
         for f in feats:
@@ -985,14 +1074,45 @@ class EmbeddingEngine:
                 return False
         return not all(getattr(f, "is_single", False) for f in feats)
 
-    def _bag_host_buffer(self, batch, dim: int, feats):
+    def _one_call(self, dim: int) -> bool:
+        """A group of this dim can be looked up in one native call: CUDA
+        device, a store with the fused entry points, not distributed (nor
+        PA_FORCE_DIST), no spill tier."""
+        store = self.stores[dim]
+        return (
+            self.device.type == "cuda"
+            and store.fused_native
+            and not (self.dist.distributed or self._force_dist)
+            and store.spill is None
+        )
+
+    def _raw_group(self, dim: int, feats) -> bool:
+        """The raw-path shape: a one-call group (_one_call) with at least one
+        raw slot, no slot (sum or raw) with hashstack rounds, and PA_RAW_FAST
+        on.  Its sum slots ride along, single-ID or bags."""
+        if not (self._raw_fast and self._one_call(dim)):
+            return False
+        cfgs = [self.schema.get_slot(f.name) for f in feats]
+        return any(not c.embedding_summation for c in cfgs) and all(
+            c.hash_stack_rounds == 0 for c in cfgs
+        )
+
+    def _sums_first(self, feats) -> List:
+        """A group's features, sum slots first, then raw slots; each part in
+        its incoming order."""
+        return sorted(
+            feats,
+            key=lambda f: not self.schema.get_slot(f.name).embedding_summation,
+        )
+
+    def _bag_host_buffer(self, batch, dim: int, feats, kind: str = "bag"):
         """A bag group's staging buffer (pack_bag_buffer), built and checked
-        once per (batch, dim-group) and kept in the batch's pinned cache:
-        -> (i64 tensor, nnz, B).  Pinned on the GPU path."""
+        once per (batch, dim-group) and kept in the batch's pinned cache under
+        ``(kind, dim)``: -> (i64 tensor, nnz, B).  Pinned on the GPU path."""
         pc = getattr(batch, "_pinned_cache", None)
         if pc is None:
             pc = batch._pinned_cache = {}
-        hit = pc.get(("bag", dim))
+        hit = pc.get((kind, dim))
         if hit is None:
             made = []
 
@@ -1004,7 +1124,7 @@ class EmbeddingEngine:
                 return made[0].numpy()
 
             _buf, nnz, B = pack_bag_buffer(feats, alloc)
-            hit = pc[("bag", dim)] = (made[0], nnz, B)
+            hit = pc[(kind, dim)] = (made[0], nnz, B)
         return hit
 
     def _padded_a2a(self, store) -> bool:
@@ -1183,6 +1303,68 @@ class EmbeddingEngine:
             self._tick("native", t0)
         return group
 
+    def _process_group_raw(self, dim: int, feats, out: PersiaTrainingBatch,
+                           train: bool, batch: PersiaBatch) -> _GroupCtx:
+        """Raw path: a single-GPU group with raw (sequence) slots, whose sum
+        slots (single-ID or bags) ride along.  The bag path's upload over all
+        the slots, sum slots first, and one native call that also writes each
+        raw slot's fixed-size ``(B, sfs, dim)`` rows and mask straight from
+        the arena.  No host sync.  ``sum_base`` of the group it leaves is the
+        whole leaf base: the sum segments, then every raw slot's cell rows,
+        which ``seg_id`` sends the raw positions to (-1 past sfs), so
+        ``update_local`` takes the group as it takes a bag group."""
+        timing = self._prod_timing
+        if timing:
+            t0 = time.perf_counter()
+        feats = self._sums_first(feats)
+        pin, nnz, B = self._bag_host_buffer(batch, dim, feats, kind="raw")
+        names = tuple(f.name for f in feats)
+        plan = self._plans.get(("raw", dim, names, B))
+        if plan is None:
+            plan = self._plans[("raw", dim, names, B)] = _RawPlan(
+                dim, [self.schema.get_slot(n) for n in names], B, self.device
+            )
+        S, n_slots = plan.S, len(feats)
+        upload = pin.to(self.device, non_blocking=True)
+        if timing:
+            t0 = self._tick("prep", t0)
+        (base, mask, uniq, inverse, perm, ustarts, u_count, slot_hint,
+         src_hint, cat_offsets, seg_id, seg_lens, fwd_scale,
+         raw_num) = self.stores[dim].lookup_local_raw(
+            upload, nnz, S, B, plan.prefixes, self._spacing_arg,
+            plan.sqrt_flags, plan.raw_meta, plan.sfs,
+            train and self._update_hints, train,
+        )
+        starts = pin.numpy()[nnz : nnz + n_slots + 1]
+        offsets = upload[nnz + n_slots + 1 :].view(n_slots, B + 1)
+        slot_ctxs = []
+        for i, f in enumerate(feats):
+            sc = _SlotCtx(
+                name=f.name, cfg=self.schema.get_slot(f.name),
+                pos_slice=(int(starts[i]), int(starts[i + 1])),
+                seg_offsets=offsets[i],
+            )
+            if i < S:
+                sc.sum_seg_base = i * B
+            else:
+                sc.raw_row_base = plan.row_bases[i - S]
+                sc.raw_sfs = plan.sfs[i - S]
+            slot_ctxs.append(sc)
+        group = _GroupCtx(
+            dim=dim, uniq_keys=uniq, inverse=inverse, perm=perm,
+            ustarts=ustarts, u_count=u_count, slots=slot_ctxs,
+            cat_offsets=cat_offsets, seg_id=seg_id, seg_lens=seg_lens,
+            sqrt_mask=plan.sqrt_mask, sum_base=base, n_sum_slots=S,
+            has_sqrt=plan.has_sqrt, fwd_scale=fwd_scale, raw_mask=mask,
+            raw_num=raw_num,
+        )
+        if slot_hint.numel():  # both empty when none were asked for
+            group.slot_hint, group.src_hint = slot_hint, src_hint
+        out._lazy_sum_groups.append((group, list(names), B))
+        if timing:
+            self._tick("native", t0)
+        return group
+
     def _process_group(self, dim: int, feats, out: PersiaTrainingBatch, train: bool,
                        batch: PersiaBatch) -> _GroupCtx:
         native = self.device.type == "cuda"
@@ -1191,6 +1373,8 @@ class EmbeddingEngine:
             return self._process_group_fast(dim, feats, out, train, batch)
         if self._bag_group(dim, feats):
             return self._process_group_bags(dim, feats, out, train, batch)
+        if self._raw_group(dim, feats):
+            return self._process_group_raw(dim, feats, out, train, batch)
         # sum slots first so they occupy a contiguous prefix of the position
         # space (one fused segment-sum launch for the whole group)
         feats = sorted(
@@ -1390,7 +1574,9 @@ class EmbeddingEngine:
         A ``skip`` caller builds the tensor anyway, so only the others pay
         the ``any()`` readback that can spare it; a bag group knows on the
         host whether it has a sqrt slot and reuses the forward's scale
-        tensor, so it never reads anything back."""
+        tensor, so it never reads anything back.  For a raw-path group the
+        scale covers every row of the leaf base, the raw cells included (the
+        update indexes it by gradient row)."""
         mask = group.sqrt_mask
         if group.has_sqrt is not None:
             has_sqrt = group.has_sqrt
@@ -1400,10 +1586,11 @@ class EmbeddingEngine:
             )
         if skip is None and loss_scale == 1.0 and not has_sqrt:
             return self._empty_scale
-        scale = torch.full(
-            (group.cat_offsets.numel() - 1,), 1.0 / loss_scale,
-            device=self.device,
+        n_rows = (
+            group.sum_base.shape[0] if group.raw_mask is not None
+            else group.cat_offsets.numel() - 1
         )
+        scale = torch.full((n_rows,), 1.0 / loss_scale, device=self.device)
         if has_sqrt:
             sqrt_scale = group.fwd_scale
             if sqrt_scale is None:
@@ -1429,8 +1616,8 @@ class EmbeddingEngine:
         -> whether any slot contributed."""
         added = False
         for sc in group.slots:
-            if sc.cfg.embedding_summation:
-                continue
+            if sc.cfg.embedding_summation or sc.raw_sfs:
+                continue  # raw-path slots ride in the group's base
             g = grads.get(sc.name)
             if g is None or self._nan_slot(sc, g):
                 continue
@@ -1453,7 +1640,10 @@ class EmbeddingEngine:
     ) -> None:
         """grads: slot name -> grad tensor ((B,dim) f16 for sum slots,
         (U_slot, dim) f32 for raw slots — the contract of ctx._on_backward,
-        reference persia/ctx.py:926-1005) or None (skipped)."""
+        reference persia/ctx.py:926-1005) or None (skipped).  A raw-path slot
+        (``SlotPayload.raw_rows``) takes the gradient of its rows instead,
+        (B, sfs, dim) or (B*sfs, dim) f16, and is handled as the sum slots
+        are."""
         self._apply_slot_grads(training_batch, grads, loss_scale)
 
     def _apply_slot_grads(self, training_batch, grads, loss_scale) -> None:
@@ -1465,7 +1655,8 @@ class EmbeddingEngine:
             buf = torch.zeros(U, group.dim, dtype=torch.float32, device=self.device)
             sum_slots = [
                 sc for sc in group.slots
-                if sc.cfg.embedding_summation and grads.get(sc.name) is not None
+                if (sc.cfg.embedding_summation or sc.raw_sfs)
+                and grads.get(sc.name) is not None
             ]
             # no sum-slot grads at all: no fused launch, so a fully skipped
             # group never applies a zero-gradient optimizer step (reference
@@ -1478,16 +1669,17 @@ class EmbeddingEngine:
                 # (NaN*0 would still be NaN); a None slot is a skipped one.
                 g_parts, flag_parts = [], []
                 for sc in group.slots:
-                    if not sc.cfg.embedding_summation:
+                    if not (sc.cfg.embedding_summation or sc.raw_sfs):
                         continue
+                    n = B * (sc.raw_sfs or 1)  # the slot's rows of the base
                     g = grads.get(sc.name)
                     if g is None:
-                        g = torch.zeros(B, group.dim, dtype=torch.float16, device=self.device)
+                        g = torch.zeros(n, group.dim, dtype=torch.float16, device=self.device)
                         flag = torch.ones((), dtype=torch.bool, device=self.device)
                     else:
                         flag = torch.isnan(g).any()
-                    g_parts.append(g.to(torch.float16))
-                    flag_parts.append(flag.expand(B))
+                    g_parts.append(g.to(torch.float16).reshape(n, group.dim))
+                    flag_parts.append(flag.expand(n))
                 scale = self._seg_scale(group, loss_scale, skip=torch.cat(flag_parts))
                 self._C.grad_scatter(
                     torch.nan_to_num(torch.cat(g_parts, dim=0)).contiguous(),

@@ -21,7 +21,7 @@ Two implementations with identical semantics:
   also the CPU execution backend).
 * :class:`HipEmbeddingStore` — HBM-resident, HIP kernels via persia_amd._C.
 """
-from typing import Iterator, Optional, Tuple
+from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -171,8 +171,8 @@ class EmbeddingStoreBase:
     """One rank's shard for one dim-group of slots."""
 
     # True where the backend has the fused entry points the engine's
-    # sync-free paths call: lookup_local, lookup_local_bags, update_local,
-    # scatter_update
+    # sync-free paths call: lookup_local, lookup_local_bags, lookup_local_raw,
+    # update_local, scatter_update
     fused_native = False
 
     def __init__(
@@ -770,6 +770,29 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         return self._C.lookup_local_bags(
             upload, nnz, S, B, prefixes, spacing_arg, sqrt_flags, int(hints),
             self.keys, self.ticks, self.arena,
+            *self._lookup_args(train, self.next_tick()),
+        )
+
+    def lookup_local_raw(self, upload: torch.Tensor, nnz: int, S: int, B: int,
+                         prefixes: torch.Tensor, spacing_arg: int,
+                         sqrt_flags: torch.Tensor, raw_meta: torch.Tensor,
+                         sfs: List[int], hints: bool, train: bool):
+        """The whole single-GPU lookup of a group with raw (sequence) slots in
+        one native call: ``S`` sum slots first (single-ID or bags), then one
+        raw slot per entry of ``sfs`` (its ``sample_fixed_size``).  ``upload``
+        is ``lookup_local_bags``' buffer over all the slots; ``raw_meta`` is
+        the device i64 ``row_base[R] ‖ sfs[R]`` (engine ``raw_slot_meta``).
+        -> (base, mask, uniq, inverse, perm, ustarts, u_count, slot_hint,
+        src_hint, cat_offsets, seg_id, seg_lens, seg_scale, raw_num).
+        ``base`` f16 ``[S*B + sum B*sfs, dim]`` holds the sums, then each raw
+        slot's cell rows sample-major; ``mask`` f16 ``[sum B*sfs]`` is 1 where
+        a cell holds an id (a missing row included).  ``seg_id`` sends a
+        position to its gradient row in ``base``, -1 for a truncated one;
+        ``seg_scale`` covers ``base``'s rows or is empty without a sqrt slot;
+        ``raw_num`` i64 ``[R*B]`` is ``min(len, sfs)``."""
+        return self._C.lookup_local_raw(
+            upload, nnz, S, B, prefixes, spacing_arg, sqrt_flags, raw_meta,
+            list(sfs), int(hints), self.keys, self.ticks, self.arena,
             *self._lookup_args(train, self.next_tick()),
         )
 

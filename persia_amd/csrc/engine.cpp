@@ -32,6 +32,19 @@ std::vector<torch::Tensor> store_lookup_bags(
     torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
     double hi, double admit_prob, double state_init, int64_t opt_space,
     torch::Tensor u_count, torch::Tensor seg_id);
+std::vector<torch::Tensor> raw_plan(torch::Tensor plan, int64_t S, int64_t B,
+                                    int64_t nnz, torch::Tensor sqrt_flags,
+                                    torch::Tensor raw_meta,
+                                    std::vector<int64_t> sfs);
+std::vector<torch::Tensor> store_lookup_raw(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor inverse, torch::Tensor perm,
+    torch::Tensor ustarts, torch::Tensor cat_offsets, torch::Tensor seg_scale,
+    torch::Tensor plan, torch::Tensor raw_meta, std::vector<int64_t> sfs,
+    int64_t S, int64_t B, torch::Tensor base, torch::Tensor mask, int64_t dim,
+    int64_t train, int64_t tick, double lo, double hi, double admit_prob,
+    double state_init, int64_t opt_space, torch::Tensor u_count,
+    torch::Tensor seg_id);
 void store_update(torch::Tensor table_keys, torch::Tensor ticks,
                   torch::Tensor arena, torch::Tensor query,
                   torch::Tensor grads, int64_t dim, int64_t opt,
@@ -204,6 +217,72 @@ std::vector<torch::Tensor> lookup_local_bags(
       u_count, want_hints ? seg_id : seg_id.narrow(0, 0, 0));
   return {sums,       uniq, inverse,     perm,   ustarts, u_count,
           h[0],       h[1], cat_offsets, seg_id, p[2],    p[3]};
+}
+
+// Single-GPU fused lookup of a raw group: S sum slots (single-ID or bags),
+// then R = sfs.size() raw (sequence) slots, whose output is the fixed-size
+// tensor [B, sfs[r], dim] and a 0/1 mask per cell.  `upload` is the group's
+// one H2D buffer in lookup_local_bags' layout over all S+R slots,
+//   values[nnz] ‖ slot_starts[S+R+1] ‖ offsets[S+R, B+1]
+// raw_meta is the device copy of row_base[R] ‖ sfs[R] (raw_plan).  sign prep
+// -> padded dedup -> plan -> probe/claim -> init launch (training) -> sums,
+// then the raw cells, both straight from the arena.  No host sync.  A
+// position past sfs in its sample is looked up and inserted like any other; it
+// feeds no cell and its seg_id is -1.
+// Returns {base f16 [S*B + sum_r B*sfs[r], dim] (sums, then each raw slot's
+// cell rows, sample-major), mask f16 [sum_r B*sfs[r]], uniq, inverse, perm,
+// ustarts, u_count, slot_hint, src_hint, cat_offsets, seg_id, seg_lens,
+// seg_scale, raw_num}: cat_offsets and seg_lens cover the sum region, seg_id
+// all positions; seg_scale covers base's rows (1 over the raw rows) or is empty
+// without a sqrt slot; raw_num i64[R*B] is min(len, sfs) per raw sample.
+std::vector<torch::Tensor> lookup_local_raw(
+    torch::Tensor upload, int64_t nnz, int64_t S, int64_t B,
+    torch::Tensor prefixes, int64_t spacing, torch::Tensor sqrt_flags,
+    torch::Tensor raw_meta, std::vector<int64_t> sfs, int64_t hints,
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    int64_t dim, int64_t train, int64_t tick, double lo, double hi,
+    double admit_prob, double state_init, int64_t opt_space) {
+  const int64_t R = (int64_t)sfs.size();
+  const int64_t n_slots = S + R;
+  TORCH_CHECK(S >= 0 && R >= 1 && B >= 0 && nnz >= 0 &&
+                  upload.scalar_type() == torch::kInt64 &&
+                  upload.is_contiguous() &&
+                  upload.numel() == nnz + n_slots + 1 + n_slots * (B + 1),
+              "lookup_local_raw: upload must be "
+              "i64[nnz + S+R+1 + (S+R)*(B+1)]");
+  TORCH_CHECK(prefixes.numel() == n_slots,
+              "lookup_local_raw: prefixes must be [S+R]");
+  // the thread-per-position limit of lookup_local_bags
+  TORCH_CHECK(nnz <= (int64_t)16384 * 256,
+              "lookup_local_raw: ", nnz, " ids in one dim-group, the "
+              "thread-per-position kernels cover 4194304");
+  auto values = upload.narrow(0, 0, nnz);
+  auto slot_starts = upload.narrow(0, nnz, n_slots + 1);
+  auto plan = upload.narrow(0, nnz, n_slots + 1 + n_slots * (B + 1));
+  auto keys = sign_prep(values, slot_starts, prefixes, spacing);
+  auto d = dedup_padded(keys);
+  auto& uniq = d[0];
+  auto& inverse = d[1];
+  auto& perm = d[2];
+  auto& ustarts = d[3];
+  auto& u_count = d[4];
+  auto p = raw_plan(plan, S, B, nnz, sqrt_flags, raw_meta, sfs);
+  auto& cat_offsets = p[0];
+  auto& seg_id = p[1];
+  int64_t n_cells = 0;
+  for (int64_t f : sfs) n_cells += B * f;
+  auto f16 =
+      torch::TensorOptions().dtype(torch::kFloat16).device(upload.device());
+  auto base = torch::empty({S * B + n_cells, dim}, f16);
+  auto mask = torch::empty({n_cells}, f16);
+  const bool want_hints = train && hints;
+  auto h = store_lookup_raw(
+      table_keys, ticks, arena, uniq, inverse, perm, ustarts, cat_offsets,
+      p[3], plan, raw_meta, sfs, S, B, base, mask, dim, train, tick, lo, hi,
+      admit_prob, state_init, opt_space, u_count,
+      want_hints ? seg_id : seg_id.narrow(0, 0, 0));
+  return {base, mask, uniq,        inverse, perm, ustarts, u_count,
+          h[0], h[1], cat_offsets, seg_id,  p[2], p[3],    p[4]};
 }
 
 // Single-GPU fused backward: per-segment grads -> per-sign scatter -> fused
@@ -388,6 +467,10 @@ void init_engine(pybind11::module_& m) {
   m.def("lookup_local_bags", &lookup_local_bags,
         "fused single-GPU lookup of a multi-ID sum group (sign prep + dedup + "
         "segment plan + probe + init + sums from the arena)");
+  m.def("lookup_local_raw", &lookup_local_raw,
+        "fused single-GPU lookup of a group with raw (sequence) slots (sign "
+        "prep + dedup + plan + probe + init + sums and raw cells from the "
+        "arena)");
   m.def("update_local", &update_local,
         "fused single-GPU backward (scatter + optimizer update)");
 }

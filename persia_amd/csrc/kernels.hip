@@ -665,27 +665,45 @@ __global__ void segment_sum_kernel(const RowT* __restrict__ rows,
 // ------------------------------------------------ bag (multi-ID) sum lookup
 
 // Segment plan of a bag group, from the uploaded per-slot CSR.  `plan` is
-// slot_starts[S+1] followed by offsets[S, B+1] (each slot's offsets relative
-// to its start; the host builder has checked them: first 0, non-decreasing,
-// last == the slot's length).  Segment s*B+b is sample b of slot s.
-//   cat_offsets[s*B+b] = slot_starts[s] + offsets[s][b],  cat_offsets[S*B] = nnz
+// slot_starts[S+R+1] followed by offsets[S+R, B+1] (each slot's offsets
+// relative to its start; the host builder has checked them: first 0,
+// non-decreasing, last == the slot's length).  The first S slots are sum
+// slots: segment s*B+b is sample b of slot s.
+//   cat_offsets[s*B+b] = slot_starts[s] + offsets[s][b]
+//   cat_offsets[S*B]   = slot_starts[S]   (nnz without raw slots)
 //   seg_id[p]          = segment of position p
 //   seg_lens[seg]      = (float)len
 //   seg_scale[seg]     = sqrt slot ? rsqrtf(max(len, 1)) : 1   (optional)
 // Thread i serves segment i and position i.  A position finds its slot and
 // sample by binary search (the last start <= p: empty slots and empty bags
 // repeat a start, and the position belongs behind them).
+//
+// The R slots behind them are raw (sequence) slots, R = 0 for a pure bag
+// group.  raw_meta is row_base[R] followed by sfs[R]: raw slot r owns the
+// B*sfs[r] rows from row_base[r] on, one per cell (sample b, column c), in
+// the group's gradient-row space of n_rows rows (sum segments first).  A raw
+// position with column c = q - offsets[b] feeds cell row_base + b*sfs + c, or
+// nothing (-1) when it is truncated (c >= sfs); a cell is a segment of at
+// most one position.
+//   seg_id[p]          = c < sfs ? row_base[r] + b*sfs[r] + c : -1
+//   seg_scale[row]     = 1 over the raw rows (the update indexes it by row)
+//   raw_num[r*B+b]     = min(len, sfs[r])
 __global__ void bag_plan_kernel(const int64_t* __restrict__ plan,
                                 const int* __restrict__ sqrt_flags, int S,
                                 int64_t B, int64_t nnz,
                                 int64_t* __restrict__ cat_offsets,
                                 int64_t* __restrict__ seg_id,
                                 float* __restrict__ seg_lens,
-                                float* __restrict__ seg_scale) {
+                                float* __restrict__ seg_scale, int R,
+                                const int64_t* __restrict__ raw_meta,
+                                int64_t n_rows,
+                                int64_t* __restrict__ raw_num) {
   const int64_t n_seg = (int64_t)S * B;
-  const int64_t n = n_seg + 1 > nnz ? n_seg + 1 : nnz;
+  const int64_t n_raw = (int64_t)R * B;
+  const int64_t n_head = (R ? n_rows : n_seg) + 1;  // n_rows >= n_seg + n_raw
+  const int64_t n = n_head > nnz ? n_head : nnz;
   const int64_t* slot_starts = plan;
-  const int64_t* offsets = plan + S + 1;
+  const int64_t* offsets = plan + S + R + 1;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (i < n_seg) {
@@ -697,11 +715,18 @@ __global__ void bag_plan_kernel(const int64_t* __restrict__ plan,
       if (seg_scale)
         seg_scale[i] =
             sqrt_flags[s] ? rsqrtf(fmaxf((float)len, 1.0f)) : 1.0f;
-    } else if (i == n_seg) {
-      cat_offsets[i] = nnz;
+    } else {
+      if (i == n_seg) cat_offsets[i] = slot_starts[S];
+      if (seg_scale && i < n_rows) seg_scale[i] = 1.0f;
+    }
+    if (i < n_raw) {
+      const int64_t r = i / B, b = i % B;
+      const int64_t* off = offsets + (S + r) * (B + 1);
+      const int64_t len = off[b + 1] - off[b], sfs = raw_meta[R + r];
+      raw_num[i] = len < sfs ? len : sfs;
     }
     if (i < nnz) {
-      int lo = 0, hi = S;  // slot_starts[lo] <= i < slot_starts[lo + 1]
+      int lo = 0, hi = S + R;  // slot_starts[lo] <= i < slot_starts[lo + 1]
       while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (i >= slot_starts[mid]) lo = mid; else hi = mid;
@@ -713,7 +738,12 @@ __global__ void bag_plan_kernel(const int64_t* __restrict__ plan,
         const int64_t mid = (blo + bhi) >> 1;
         if (q >= off[mid]) blo = mid; else bhi = mid;
       }
-      seg_id[i] = (int64_t)lo * B + blo;
+      if (lo < S) {
+        seg_id[i] = (int64_t)lo * B + blo;
+      } else {
+        const int64_t c = q - off[blo], sfs = raw_meta[R + lo - S];
+        seg_id[i] = c < sfs ? raw_meta[lo - S] + blo * sfs + c : -1;
+      }
     }
   }
 }
@@ -790,6 +820,110 @@ __global__ void bag_sum_kernel(const float* __restrict__ arena,
       for (int t = 0; t < T; ++t)
         if (cb + t * L.st < dim)
           dst[cb + t * L.st] = __float2half(acc[t] * scale);
+    }
+  }
+}
+
+// ------------------------------------------------ raw (sequence) slot gather
+
+// The fixed-size tensor of the raw slots of a group, straight from the arena.
+// Cell (r, b, c) is row row_base[r] + b*sfs[r] + c of `out` (the group's leaf
+// base, sum rows first) and entry row - S*B of `mask`; with len the length of
+// sample b in slot r,
+//   c < len : f16(arena[slots[inverse[start_r + off[b] + c]]]), mask 1; a
+//             slot < 0 (miss, not admitted) gives a +0 row, the mask stays 1
+//   c >= len: +0 row, mask 0
+// `plan` and raw_meta are bag_plan_kernel's.  A wave item is one chunk of
+// G * PA_RAW_DEPTH consecutive cells of one sample (G = 64/dim cells side by
+// side for the dims pa_lanes packs): items are numbered slot-major, then
+// sample, then chunk, so a wave finds its slot by walking the R chunk counts.
+//
+// bag_sum_kernel's load chain with one addend per cell: the index, slot and
+// row loads of a lane's PA_RAW_DEPTH cells are issued level by level, all
+// unconditional (an absent cell re-reads position 0, a missing row reads row
+// 0, and the value is replaced by +0), before the first store.  The kernel
+// walks cells, not unique keys, so it never reads the unique count.  The
+// caller launches it only when the group has at least one id, in blocks of
+// 256 threads (the launch bound keeps the 8-column instantiation out of
+// scratch).
+#define PA_RAW_DEPTH 4
+template <int T>
+__global__ void __launch_bounds__(256) raw_gather_kernel(const float* __restrict__ arena,
+                                  const long long* __restrict__ slots,
+                                  const int64_t* __restrict__ inverse,
+                                  const int64_t* __restrict__ plan,
+                                  const int64_t* __restrict__ raw_meta,
+                                  __half* __restrict__ out,
+                                  __half* __restrict__ mask, int S, int R,
+                                  int64_t B, int64_t n_rows, unsigned n_items,
+                                  int dim, int row_width) {
+  const int wave = threadIdx.x / PA_WAVE;
+  const int lane = threadIdx.x % PA_WAVE;
+  const int waves_per_block = blockDim.x / PA_WAVE;
+  const PaLanes L = pa_lanes(lane, dim);
+  const unsigned CH = (unsigned)L.G * PA_RAW_DEPTH;  // cells per wave item
+  const int64_t* slot_starts = plan;
+  const int64_t* offsets = plan + S + R + 1;
+  const int64_t n_sum_rows = (int64_t)S * B;
+  for (unsigned w = blockIdx.x * waves_per_block + wave; w < n_items;
+       w += gridDim.x * waves_per_block) {
+    int r = 0;
+    unsigned rem = w;
+    int64_t sfs = raw_meta[R];
+    unsigned nch = ((unsigned)sfs + CH - 1) / CH;  // chunks per sample
+    while (r < R - 1 && rem >= (unsigned)B * nch) {
+      rem -= (unsigned)B * nch;
+      ++r;
+      sfs = raw_meta[R + r];
+      nch = ((unsigned)sfs + CH - 1) / CH;
+    }
+    const int64_t b = rem / nch;
+    if (b >= B) continue;
+    const int64_t c_base = (int64_t)(rem % nch) * CH;
+    const int64_t* off = offsets + (int64_t)(S + r) * (B + 1);
+    const int64_t p0 = slot_starts[S + r] + off[b];
+    const int64_t len = off[b + 1] - off[b];
+    const int64_t row0 = raw_meta[r] + b * sfs;  // cell (r, b, 0)
+    int64_t c[PA_RAW_DEPTH];
+    bool present[PA_RAW_DEPTH];
+#pragma unroll
+    for (int j = 0; j < PA_RAW_DEPTH; ++j) {
+      c[j] = c_base + j * L.G + L.sub;
+      present[j] = c[j] < len && c[j] < sfs;
+    }
+    for (int cb = L.c0; cb < dim; cb += T * L.st) {
+      int col[T];  // a column past dim re-reads cb; it is never stored
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        col[t] = (cb + t * L.st < dim) ? cb + t * L.st : cb;
+      int64_t u[PA_RAW_DEPTH];
+      long long sl[PA_RAW_DEPTH];
+      float v[PA_RAW_DEPTH][T];
+#pragma unroll
+      for (int j = 0; j < PA_RAW_DEPTH; ++j)
+        u[j] = inverse[present[j] ? p0 + c[j] : 0];
+#pragma unroll
+      for (int j = 0; j < PA_RAW_DEPTH; ++j) sl[j] = slots[u[j]];
+#pragma unroll
+      for (int j = 0; j < PA_RAW_DEPTH; ++j) {
+        const float* row =
+            arena + (int64_t)(sl[j] >= 0 ? sl[j] : 0) * row_width;
+#pragma unroll
+        for (int t = 0; t < T; ++t) v[j][t] = row[col[t]];
+      }
+#pragma unroll
+      for (int j = 0; j < PA_RAW_DEPTH; ++j) {
+        const int64_t cell = row0 + c[j];
+        if (c[j] >= sfs || cell < n_sum_rows || cell >= n_rows) continue;
+        const bool live = present[j] && sl[j] >= 0;
+        __half* dst = out + cell * dim;
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+          if (cb + t * L.st < dim)
+            dst[cb + t * L.st] = __float2half(live ? v[j][t] : 0.0f);
+        if (cb == 0)  // the lane that holds column 0, on its first pass
+          mask[cell - n_sum_rows] = __float2half(present[j] ? 1.0f : 0.0f);
+      }
     }
   }
 }
@@ -1610,6 +1744,37 @@ std::vector<torch::Tensor> store_lookup_sums(
   return {slots, src_hint};
 }
 
+// Launch of bag_plan_kernel for S sum slots followed by R raw slots (R = 0: a
+// pure bag group; raw_meta and n_rows are then unused).
+// -> {cat_offsets i64[S*B+1], seg_id i64[nnz], seg_lens f32[S*B], seg_scale
+//     f32[S*B], [n_rows] with raw slots, or empty (all ones) without a sqrt
+//     slot, raw_num i64[R*B]}
+static std::vector<torch::Tensor> plan_launch(
+    const torch::Tensor& plan, int64_t S, int64_t R, int64_t B, int64_t nnz,
+    const torch::Tensor& sqrt_flags, const torch::Tensor& raw_meta,
+    int64_t n_rows) {
+  const bool scaled = sqrt_flags.numel() > 0;
+  auto opts = torch::TensorOptions().dtype(torch::kInt64).device(plan.device());
+  const int64_t n_seg = S * B;
+  auto cat_offsets = torch::empty({n_seg + 1}, opts);
+  auto seg_id = torch::empty({nnz}, opts);
+  auto seg_lens = torch::empty({n_seg}, opts.dtype(torch::kFloat32));
+  auto seg_scale = torch::empty({scaled ? (R ? n_rows : n_seg) : 0},
+                                opts.dtype(torch::kFloat32));
+  auto raw_num = torch::empty({R * B}, opts);
+  // >= 1: no empty launch
+  const int64_t n = std::max((R ? n_rows : n_seg) + 1, nnz);
+  hipLaunchKernelGGL(bag_plan_kernel, dim3(n_blocks_for(n, 256)), dim3(256), 0,
+                     cur_stream(), plan.data_ptr<int64_t>(),
+                     scaled ? sqrt_flags.data_ptr<int32_t>() : nullptr, (int)S,
+                     B, nnz, cat_offsets.data_ptr<int64_t>(),
+                     seg_id.data_ptr<int64_t>(), seg_lens.data_ptr<float>(),
+                     scaled ? seg_scale.data_ptr<float>() : nullptr, (int)R,
+                     R ? raw_meta.data_ptr<int64_t>() : nullptr, n_rows,
+                     raw_num.data_ptr<int64_t>());
+  return {cat_offsets, seg_id, seg_lens, seg_scale, raw_num};
+}
+
 // Segment plan of a bag group (bag_plan_kernel).  `plan` is the uploaded
 // slot_starts[S+1] ‖ offsets[S, B+1]; sqrt_flags i32[S] marks the sqrt-scaling
 // slots and is empty when the group has none.
@@ -1621,41 +1786,78 @@ std::vector<torch::Tensor> bag_plan(torch::Tensor plan, int64_t S, int64_t B,
   TORCH_CHECK(plan.scalar_type() == torch::kInt64 && plan.is_contiguous() &&
                   plan.numel() == S + 1 + S * (B + 1),
               "bag_plan: plan must be i64[S+1 + S*(B+1)]");
-  const bool scaled = sqrt_flags.numel() > 0;
-  TORCH_CHECK(!scaled || (sqrt_flags.scalar_type() == torch::kInt32 &&
-                          sqrt_flags.numel() == S),
+  TORCH_CHECK(!sqrt_flags.numel() ||
+                  (sqrt_flags.scalar_type() == torch::kInt32 &&
+                   sqrt_flags.numel() == S),
               "bag_plan: sqrt_flags must be i32[S]");
-  auto opts = torch::TensorOptions().dtype(torch::kInt64).device(plan.device());
-  const int64_t n_seg = S * B;
-  auto cat_offsets = torch::empty({n_seg + 1}, opts);
-  auto seg_id = torch::empty({nnz}, opts);
-  auto seg_lens = torch::empty({n_seg}, opts.dtype(torch::kFloat32));
-  auto seg_scale =
-      torch::empty({scaled ? n_seg : 0}, opts.dtype(torch::kFloat32));
-  const int64_t n = std::max(n_seg + 1, nnz);  // >= 1: no empty launch
-  hipLaunchKernelGGL(bag_plan_kernel, dim3(n_blocks_for(n, 256)), dim3(256), 0,
-                     cur_stream(), plan.data_ptr<int64_t>(),
-                     scaled ? sqrt_flags.data_ptr<int32_t>() : nullptr, (int)S,
-                     B, nnz, cat_offsets.data_ptr<int64_t>(),
-                     seg_id.data_ptr<int64_t>(), seg_lens.data_ptr<float>(),
-                     scaled ? seg_scale.data_ptr<float>() : nullptr);
-  return {cat_offsets, seg_id, seg_lens, seg_scale};
+  auto p = plan_launch(plan, S, 0, B, nnz, sqrt_flags, sqrt_flags, 0);
+  p.pop_back();
+  return p;
 }
 
-// Bag lookup over the unique keys of a dedup: probe/claim, a launch that only
+// Rows of the leaf base of a raw group: the S*B sum segments, then B*sfs[r]
+// cell rows per raw slot.
+static int64_t raw_group_rows(int64_t S, int64_t B,
+                              const std::vector<int64_t>& sfs) {
+  int64_t n = S * B;
+  for (int64_t f : sfs) n += B * f;
+  return n;
+}
+
+// Plan of a raw group: S sum slots, then R = sfs.size() raw (sequence) slots
+// with sample_fixed_size sfs[r] (see bag_plan_kernel).  `plan` is the uploaded
+// slot_starts[S+R+1] ‖ offsets[S+R, B+1]; raw_meta is the device copy of
+// row_base[R] ‖ sfs[R], row_base[r] = S*B + sum_{r' < r} B*sfs[r'].
+// -> bag_plan's four tensors, seg_scale sized by the base's rows (1 over the
+//    raw rows), and raw_num i64[R*B] = min(len, sfs)
+std::vector<torch::Tensor> raw_plan(torch::Tensor plan, int64_t S, int64_t B,
+                                    int64_t nnz, torch::Tensor sqrt_flags,
+                                    torch::Tensor raw_meta,
+                                    std::vector<int64_t> sfs) {
+  const int64_t R = (int64_t)sfs.size();
+  TORCH_CHECK(S >= 0 && R >= 1 && B >= 0 && nnz >= 0, "raw_plan: bad shape");
+  for (int64_t f : sfs)
+    TORCH_CHECK(f >= 1, "raw_plan: sample_fixed_size must be positive");
+  TORCH_CHECK(plan.scalar_type() == torch::kInt64 && plan.is_contiguous() &&
+                  plan.numel() == S + R + 1 + (S + R) * (B + 1),
+              "raw_plan: plan must be i64[S+R+1 + (S+R)*(B+1)]");
+  TORCH_CHECK(!sqrt_flags.numel() ||
+                  (sqrt_flags.scalar_type() == torch::kInt32 &&
+                   sqrt_flags.numel() == S),
+              "raw_plan: sqrt_flags must be i32[S]");
+  TORCH_CHECK(raw_meta.scalar_type() == torch::kInt64 &&
+                  raw_meta.is_contiguous() && raw_meta.numel() == 2 * R &&
+                  raw_meta.device() == plan.device(),
+              "raw_plan: raw_meta must be i64[2R] on the plan's device");
+  return plan_launch(plan, S, R, B, nnz, sqrt_flags, raw_meta,
+                     raw_group_rows(S, B, sfs));
+}
+
+// The raw slots of a group behind its sum slots, for lookup_unique_sums.
+struct RawPart {
+  const torch::Tensor& plan;      // slot_starts ‖ offsets of all S+R slots
+  const torch::Tensor& raw_meta;  // row_base[R] ‖ sfs[R], device
+  const std::vector<int64_t>& sfs;
+  int64_t S, B;
+  torch::Tensor& base;  // f16 [n_rows, dim], sums first
+  torch::Tensor& mask;  // f16 [n_rows - S*B]
+};
+
+// Lookup over the unique keys of a dedup: probe/claim, a launch that only
 // initializes the freshly claimed rows (training), then the segment sums read
-// straight from the arena (bag_sum_kernel) — no [U, dim] row buffer.  The
-// init launch precedes the sum launch because a fresh row is read by every
-// segment that holds its key, not by the wave that claimed it.
+// straight from the arena (bag_sum_kernel) — no [U, dim] row buffer — and,
+// with `raw`, the raw slots' cells (raw_gather_kernel).  The init launch
+// precedes the reading launches because a fresh row is read by every segment
+// and cell that holds its key, not by the wave that claimed it.
 // Returns the update hints {slot_hint, src_hint} as store_lookup_sums does:
 // both empty unless seg_id is given.
-std::vector<torch::Tensor> store_lookup_bags(
+static std::vector<torch::Tensor> lookup_unique_sums(
     torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
     torch::Tensor query, torch::Tensor inverse, torch::Tensor perm,
     torch::Tensor ustarts, torch::Tensor cat_offsets, torch::Tensor seg_scale,
     torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
     double hi, double admit_prob, double state_init, int64_t opt_space,
-    torch::Tensor u_count, torch::Tensor seg_id) {
+    torch::Tensor u_count, torch::Tensor seg_id, const RawPart* raw) {
   const int64_t n = query.numel();
   const int64_t n_seg = cat_offsets.numel() - 1;
   auto opts = torch::TensorOptions().dtype(torch::kInt64).device(query.device());
@@ -1666,12 +1868,16 @@ std::vector<torch::Tensor> store_lookup_bags(
   TORCH_CHECK(sums.size(0) == n_seg && sums.size(1) == dim &&
                   sums.is_contiguous(),
               "store_lookup_bags: sums must be [n_seg, dim]");
-  TORCH_CHECK(!seg_scale.numel() || seg_scale.numel() == n_seg,
+  TORCH_CHECK(!seg_scale.numel() || seg_scale.numel() >= n_seg,
               "store_lookup_bags: seg_scale must be empty or [n_seg]");
   TORCH_CHECK(!hints || seg_id.numel() >= n,
               "store_lookup_bags: seg_id shorter than perm");
   if (n == 0) {  // every bag empty: nothing to probe, the sums are zeros
     sums.zero_();
+    if (raw) {
+      raw->base.zero_();
+      raw->mask.zero_();
+    }
     return {src_hint, src_hint};
   }
   auto slots = torch::empty({n}, opts);
@@ -1700,9 +1906,9 @@ std::vector<torch::Tensor> store_lookup_bags(
                        is_new.data_ptr<int32_t>(), (float*)nullptr, n,
                        (int)dim, row_width, lo, hi, (float)state_init, nullptr,
                        nullptr, n_dev);
+  const bool packed = dim < PA_WAVE && (PA_WAVE % dim) == 0;
   if (n_seg > 0) {
     const dim3 grid(n_blocks_for(n_seg, 4)), block(256);
-    const bool packed = dim < PA_WAVE && (PA_WAVE % dim) == 0;
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, block, 0, st, arena.data_ptr<float>(),
                          (const long long*)slots.data_ptr<int64_t>(),
@@ -1718,8 +1924,95 @@ std::vector<torch::Tensor> store_lookup_bags(
     else if (dim <= 4 * PA_WAVE) launch(bag_sum_kernel<4>);
     else launch(bag_sum_kernel<8>);
   }
+  if (raw) {
+    // wave items: per raw slot, B samples times the chunks of one sample
+    const int64_t chunk = (packed ? PA_WAVE / dim : 1) * PA_RAW_DEPTH;
+    int64_t n_items = 0;
+    for (int64_t f : raw->sfs) n_items += raw->B * ((f + chunk - 1) / chunk);
+    if (n_items > 0) {
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(
+            kernel, dim3(n_blocks_for(n_items, 4)), dim3(256), 0, st,
+            arena.data_ptr<float>(),
+            (const long long*)slots.data_ptr<int64_t>(),
+            inverse.data_ptr<int64_t>(), raw->plan.data_ptr<int64_t>(),
+            raw->raw_meta.data_ptr<int64_t>(),
+            (__half*)raw->base.data_ptr<at::Half>(),
+            (__half*)raw->mask.data_ptr<at::Half>(), (int)raw->S,
+            (int)raw->sfs.size(), raw->B, raw->base.size(0),
+            (unsigned)n_items, (int)dim, row_width);
+      };
+      if (packed || dim <= PA_WAVE) launch(raw_gather_kernel<1>);
+      else if (dim <= 2 * PA_WAVE) launch(raw_gather_kernel<2>);
+      else if (dim <= 4 * PA_WAVE) launch(raw_gather_kernel<4>);
+      else launch(raw_gather_kernel<8>);
+    }
+  }
   if (!hints) return {src_hint, src_hint};  // slots was a temporary
   return {slots, src_hint};
+}
+
+// Bag lookup over the unique keys of a dedup (lookup_unique_sums without raw
+// slots).
+std::vector<torch::Tensor> store_lookup_bags(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor inverse, torch::Tensor perm,
+    torch::Tensor ustarts, torch::Tensor cat_offsets, torch::Tensor seg_scale,
+    torch::Tensor sums, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space,
+    torch::Tensor u_count, torch::Tensor seg_id) {
+  TORCH_CHECK(!seg_scale.numel() ||
+                  seg_scale.numel() == cat_offsets.numel() - 1,
+              "store_lookup_bags: seg_scale must be empty or [n_seg]");
+  return lookup_unique_sums(table_keys, ticks, arena, query, inverse, perm,
+                            ustarts, cat_offsets, seg_scale, sums, dim, train,
+                            tick, lo, hi, admit_prob, state_init, opt_space,
+                            u_count, seg_id, nullptr);
+}
+
+// Lookup of a raw group over the unique keys of its dedup: S sum slots as
+// store_lookup_bags, then the R = sfs.size() raw slots' cells into the rows
+// of `base` behind the S*B sums and into `mask` (raw_gather_kernel).  `plan`,
+// raw_meta and sfs are raw_plan's; seg_scale is empty or covers base's rows.
+std::vector<torch::Tensor> store_lookup_raw(
+    torch::Tensor table_keys, torch::Tensor ticks, torch::Tensor arena,
+    torch::Tensor query, torch::Tensor inverse, torch::Tensor perm,
+    torch::Tensor ustarts, torch::Tensor cat_offsets, torch::Tensor seg_scale,
+    torch::Tensor plan, torch::Tensor raw_meta, std::vector<int64_t> sfs,
+    int64_t S, int64_t B, torch::Tensor base, torch::Tensor mask, int64_t dim,
+    int64_t train, int64_t tick, double lo, double hi, double admit_prob,
+    double state_init, int64_t opt_space, torch::Tensor u_count,
+    torch::Tensor seg_id) {
+  const int64_t R = (int64_t)sfs.size();
+  const int64_t n_rows = raw_group_rows(S, B, sfs);
+  TORCH_CHECK(S >= 0 && R >= 1 && B >= 0 && cat_offsets.numel() - 1 == S * B,
+              "store_lookup_raw: bad shape");
+  for (int64_t f : sfs)
+    TORCH_CHECK(f >= 1, "store_lookup_raw: sample_fixed_size must be positive");
+  // raw_gather numbers its wave items and cells with 32 bits
+  TORCH_CHECK(n_rows < ((int64_t)1 << 31), "store_lookup_raw: ", n_rows,
+              " rows in one group");
+  TORCH_CHECK(plan.scalar_type() == torch::kInt64 && plan.is_contiguous() &&
+                  plan.numel() == S + R + 1 + (S + R) * (B + 1),
+              "store_lookup_raw: plan must be i64[S+R+1 + (S+R)*(B+1)]");
+  TORCH_CHECK(raw_meta.scalar_type() == torch::kInt64 &&
+                  raw_meta.is_contiguous() && raw_meta.numel() == 2 * R,
+              "store_lookup_raw: raw_meta must be i64[2R]");
+  TORCH_CHECK(base.scalar_type() == torch::kFloat16 && base.is_contiguous() &&
+                  base.dim() == 2 && base.size(0) == n_rows &&
+                  base.size(1) == dim,
+              "store_lookup_raw: base must be f16 [S*B + sum B*sfs, dim]");
+  TORCH_CHECK(mask.scalar_type() == torch::kFloat16 && mask.is_contiguous() &&
+                  mask.numel() == n_rows - S * B,
+              "store_lookup_raw: mask must be f16 [sum B*sfs]");
+  TORCH_CHECK(!seg_scale.numel() || seg_scale.numel() == n_rows,
+              "store_lookup_raw: seg_scale must be empty or cover base's rows");
+  RawPart raw{plan, raw_meta, sfs, S, B, base, mask};
+  return lookup_unique_sums(table_keys, ticks, arena, query, inverse, perm,
+                            ustarts, cat_offsets, seg_scale,
+                            base.narrow(0, 0, S * B), dim, train, tick, lo, hi,
+                            admit_prob, state_init, opt_space, u_count, seg_id,
+                            &raw);
 }
 
 torch::Tensor store_probe(torch::Tensor table_keys, torch::Tensor ticks,
@@ -2045,6 +2338,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bag group segment plan from the uploaded per-slot CSR");
   m.def("store_lookup_bags", &store_lookup_bags,
         "bag lookup: probe + init launch + segment sums read from the arena");
+  m.def("raw_plan", &raw_plan,
+        "raw group plan: bag_plan plus the cell rows of the raw slots");
+  m.def("store_lookup_raw", &store_lookup_raw,
+        "raw group lookup: store_lookup_bags + the raw slots' cells gathered "
+        "from the arena");
   m.def("store_update", &store_update, "fused sparse optimizer update");
   m.def("store_import", &store_import, "bulk insert rows (checkpoint load)");
   m.def("segment_sum", &segment_sum, "fused gather + per-sample summation");

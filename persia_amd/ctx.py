@@ -205,7 +205,15 @@ class EmbeddingCtx(BaseCtx):
         emb_tensors: List[torch.Tensor] = []
         cache = []  # (name, distinct_id_tensor, index, non_empty_index, emb_tensor)
         for p in batch.payloads:
-            if p.is_raw:
+            if p.raw_rows is not None:
+                # native raw path: the fixed-size rows are a view of the
+                # group's base (gradients flow into it like a sum slot's), so
+                # there is nothing to index-select and _on_backward has no
+                # per-slot gradient to build
+                rows = sum_views.get(p.name, p.raw_rows)
+                emb_tensors.append(torch.cat([rows, p.raw_mask], dim=2))
+                cache.append((p.name, None, None, None, rows))
+            elif p.is_raw:
                 distinct_id_tensor = p.raw_distinct
                 index_tensor = p.raw_index
                 non_empty_index = p.raw_non_empty_index
