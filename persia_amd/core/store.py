@@ -28,7 +28,7 @@ import torch
 
 from persia_amd.core import hashing
 from persia_amd.embedding import EmbeddingConfig
-from persia_amd.embedding.optim import Adagrad, Adam, Optimizer, SGD
+from persia_amd.embedding.optim import Adagrad, Adam, Ftrl, Optimizer, SGD
 
 BUCKET_SIZE = 8
 PROBE_BUCKETS = 4
@@ -454,6 +454,10 @@ class CpuEmbeddingStore(EmbeddingStoreBase):
             v = rows[:, 2 * self.dim :]
             b1p, b2p = powers
             R.adam_update(emb, m, v, g, b1p, b2p, o.lr, o.betas[0], o.betas[1], o.eps, wb)
+        elif isinstance(o, Ftrl):
+            z = rows[:, self.dim : 2 * self.dim]
+            n = rows[:, 2 * self.dim :]
+            R.ftrl_update(emb, z, n, g, o.lr, o.beta, o.l1, o.l2, wb)
         else:
             raise ValueError(f"unknown optimizer {o.kind}")
         self.arena[idx] = rows
@@ -522,7 +526,7 @@ class HipEmbeddingStore(EmbeddingStoreBase):
             self.n_slots, self.row_width, dtype=torch.float32, device=device
         )
         self._skipped = torch.zeros(2, dtype=torch.int32, device=device)  # miss, nan
-        self._opt_code = {"sgd": 0, "adagrad": 1, "adam": 2}[optimizer.kind]
+        self._opt_code = {"sgd": 0, "adagrad": 1, "adam": 2, "ftrl": 3}[optimizer.kind]
         self._probe_stream: Optional[torch.cuda.Stream] = None
         self._restore_tick: Optional[int] = None
         self._ckpt_stream: Optional[torch.cuda.Stream] = None
@@ -600,6 +604,8 @@ class HipEmbeddingStore(EmbeddingStoreBase):
             ]
         if isinstance(o, Adam):
             return [o.lr, o.betas[0], o.betas[1], o.eps, 0.0, 0.0]
+        if isinstance(o, Ftrl):
+            return [o.lr, o.beta, o.l1, o.l2, 0.0, 0.0]
         raise ValueError(o.kind)
 
     def _lookup_args(self, train: bool, tick: int):

@@ -336,7 +336,10 @@ __global__ void init_scatter2_kernel(float* __restrict__ arena,
 
 // one wave per key: probe (lane-parallel over the 32-slot window) + fused
 // row-wise optimizer + weight bound.
-// opt / p0..p3: see PaOptArgs (optim.h).
+// opt / p0..p3: see PaOptArgs (optim.h).  FTRL (opt 3) is an instantiation of
+// its own, chosen by the launcher: as one more arm next to the others it cost
+// the SGD/Adagrad/Adam code registers and a wave per SIMD.
+template <bool FTRL>
 __global__ void update_kernel(ull* __restrict__ table_keys,
                               unsigned* __restrict__ ticks,
                               float* __restrict__ arena,
@@ -383,7 +386,15 @@ __global__ void update_kernel(ull* __restrict__ table_keys,
       if (lane == 0) atomicAdd(&skipped[1], 1);
       continue;
     }
-    if (opt == 0) {  // SGD
+    if constexpr (FTRL) {
+      for (int c = lane; c < dim; c += PA_WAVE) {
+        const PaFtrlRow r =
+            pa_ftrl(oa, row[c], row[dim + c], row[2 * dim + c], g[c]);
+        row[c] = r.w;
+        row[dim + c] = r.z;
+        row[2 * dim + c] = r.n;
+      }
+    } else if (opt == 0) {  // SGD
       for (int c = lane; c < dim; c += PA_WAVE)
         row[c] = pa_sgd(oa, row[c], g[c]);
     } else if (opt == 1) {  // Adagrad
@@ -406,7 +417,7 @@ __global__ void update_kernel(ull* __restrict__ table_keys,
           row[dim + c] = pa_adagrad_acc(oa, acc, g[c]);
         }
       }
-    } else {  // Adam
+    } else if (opt == 2) {  // Adam
       for (int c = lane; c < dim; c += PA_WAVE) {
         const float m = pa_adam_m<true>(oa, row[dim + c], g[c]);
         const float v = pa_adam_v<true>(oa, row[2 * dim + c], g[c]);
@@ -1000,7 +1011,7 @@ __global__ void grad_scatter_idx_kernel(
 // (ordered, via the sort permutation) straight into registers, probe the
 // table, and apply the optimizer — no intermediate [U, dim] buffer.
 // Supports dim <= 8*PA_WAVE (register-resident grad row).
-template <bool HINTS>
+template <bool HINTS, bool FTRL>
 __global__ void scatter_update_kernel(
     ull* __restrict__ table_keys, unsigned* __restrict__ ticks,
     float* __restrict__ arena, const ull* __restrict__ uniq,
@@ -1107,7 +1118,17 @@ __global__ void scatter_update_kernel(
     // nontemporal arena traffic: each row is touched exactly once per step
     // and this kernel overlaps the dense graph on another stream — keeping
     // ~0.5 GB/step of one-shot data out of L2 leaves it to the GEMMs
-    if (opt == 0) {  // SGD
+    if constexpr (FTRL) {
+      for (int t = 0, c = c0; c < dim; c += st, ++t) {
+        const float z0 = __builtin_nontemporal_load(&row[dim + c]);
+        const float n0 = __builtin_nontemporal_load(&row[2 * dim + c]);
+        const float w0 = __builtin_nontemporal_load(&row[c]);
+        const PaFtrlRow r = pa_ftrl(oa, w0, z0, n0, acc[t]);
+        __builtin_nontemporal_store(r.w, &row[c]);
+        __builtin_nontemporal_store(r.z, &row[dim + c]);
+        __builtin_nontemporal_store(r.n, &row[2 * dim + c]);
+      }
+    } else if (opt == 0) {  // SGD
       for (int t = 0, c = c0; c < dim; c += st, ++t) {
         const float w0 = __builtin_nontemporal_load(&row[c]);
         __builtin_nontemporal_store(pa_sgd(oa, w0, acc[t]), &row[c]);
@@ -1133,7 +1154,7 @@ __global__ void scatter_update_kernel(
                                       &row[dim + c]);
         }
       }
-    } else {  // Adam
+    } else if (opt == 2) {  // Adam
       for (int t = 0, c = c0; c < dim; c += st, ++t) {
         const float m = pa_adam_m(
             oa, __builtin_nontemporal_load(&row[dim + c]), acc[t]);
@@ -1169,7 +1190,7 @@ struct PaRowRegs {
 // nontemporal arena traffic: each row is touched exactly once per step and
 // the kernel overlaps the dense graph on another stream — keeping ~0.5
 // GB/step of one-shot data out of L2 leaves it to the GEMMs
-template <int Q, int T>
+template <int Q, int T, bool FTRL>
 __device__ __forceinline__ void pa_load_rows(PaRowRegs<Q, T>& r,
                                              const PaOptArgs& oa,
                                              const bool (&ok)[Q],
@@ -1178,7 +1199,7 @@ __device__ __forceinline__ void pa_load_rows(PaRowRegs<Q, T>& r,
   PaGlobalF* rowk[Q];
 #pragma unroll
   for (int q = 0; q < Q; ++q) rowk[q] = (PaGlobalF*)rows[q];
-  const bool shared = oa.opt == 1 && pa_adagrad_shared(oa);
+  const bool shared = !FTRL && oa.opt == 1 && pa_adagrad_shared(oa);
 #pragma unroll
   for (int q = 0; q < Q; ++q)
     r.a0[q] = (shared && ok[q]) ? rowk[q][dim] : 0.0f;
@@ -1189,9 +1210,9 @@ __device__ __forceinline__ void pa_load_rows(PaRowRegs<Q, T>& r,
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       if (!ok[q]) continue;
-      if (oa.opt != 0 && !shared)
+      if (FTRL || (oa.opt != 0 && !shared))
         r.s1[q][t] = __builtin_nontemporal_load(&rowk[q][dim + c]);
-      if (oa.opt == 2)
+      if (FTRL || oa.opt == 2)
         r.s2[q][t] = __builtin_nontemporal_load(&rowk[q][2 * dim + c]);
       r.w0[q][t] = __builtin_nontemporal_load(&rowk[q][c]);
     }
@@ -1199,7 +1220,7 @@ __device__ __forceinline__ void pa_load_rows(PaRowRegs<Q, T>& r,
 }
 
 // Optimizer step of Q loaded rows (pa_load_rows) and their stores.
-template <int Q, int T>
+template <int Q, int T, bool FTRL>
 __device__ __forceinline__ void pa_step_rows(const PaRowRegs<Q, T>& r,
                                              const PaOptArgs& oa,
                                              const bool (&ok)[Q],
@@ -1209,7 +1230,22 @@ __device__ __forceinline__ void pa_step_rows(const PaRowRegs<Q, T>& r,
   PaGlobalF* rowk[Q];
 #pragma unroll
   for (int q = 0; q < Q; ++q) rowk[q] = (PaGlobalF*)rows[q];
-  if (oa.opt == 0) {  // SGD
+  if constexpr (FTRL) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int c = lane + t * PA_WAVE;
+      if (c >= dim) continue;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (!ok[q]) continue;
+        const PaFtrlRow n =
+            pa_ftrl(oa, r.w0[q][t], r.s1[q][t], r.s2[q][t], acc[q][t]);
+        __builtin_nontemporal_store(n.w, &rowk[q][c]);
+        __builtin_nontemporal_store(n.z, &rowk[q][dim + c]);
+        __builtin_nontemporal_store(n.n, &rowk[q][2 * dim + c]);
+      }
+    }
+  } else if (oa.opt == 0) {  // SGD
 #pragma unroll
     for (int t = 0; t < T; ++t) {
       const int c = lane + t * PA_WAVE;
@@ -1261,7 +1297,7 @@ __device__ __forceinline__ void pa_step_rows(const PaRowRegs<Q, T>& r,
         }
       }
     }
-  } else {  // Adam
+  } else if (oa.opt == 2) {  // Adam
 #pragma unroll
     for (int t = 0; t < T; ++t) {
       const int c = lane + t * PA_WAVE;
@@ -1283,7 +1319,7 @@ __device__ __forceinline__ void pa_step_rows(const PaRowRegs<Q, T>& r,
 // The unhinted form of the same step: per column, load the values of all Q
 // keys, then do the dependent math and store.  Nothing is held across
 // columns, which keeps the kernel without hints at its register budget.
-template <int Q, int T>
+template <int Q, int T, bool FTRL>
 __device__ __forceinline__ void pa_update_rows(const PaOptArgs& oa,
                                                const bool (&ok)[Q],
                                                float* const (&rowk)[Q],
@@ -1291,7 +1327,25 @@ __device__ __forceinline__ void pa_update_rows(const PaOptArgs& oa,
                                                int dim, int lane) {
   const int opt = oa.opt;
   // every branch below loads for all Q keys before the dependent math
-  if (opt == 0) {  // SGD
+  if constexpr (FTRL) {
+    for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
+      float w0[Q], z0[Q], n0[Q];
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        z0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][dim + c]) : 0.0f;
+        n0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][2 * dim + c]) : 0.0f;
+        w0[q] = ok[q] ? __builtin_nontemporal_load(&rowk[q][c]) : 0.0f;
+      }
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (!ok[q]) continue;
+        const PaFtrlRow r = pa_ftrl(oa, w0[q], z0[q], n0[q], acc[q][t]);
+        __builtin_nontemporal_store(r.w, &rowk[q][c]);
+        __builtin_nontemporal_store(r.z, &rowk[q][dim + c]);
+        __builtin_nontemporal_store(r.n, &rowk[q][2 * dim + c]);
+      }
+    }
+  } else if (opt == 0) {  // SGD
     for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
       float w0[Q];
 #pragma unroll
@@ -1348,7 +1402,7 @@ __device__ __forceinline__ void pa_update_rows(const PaOptArgs& oa,
         }
       }
     }
-  } else {  // Adam
+  } else if (opt == 2) {  // Adam
     for (int t = 0, c = lane; c < dim; c += PA_WAVE, ++t) {
 #pragma unroll
       for (int q = 0; q < Q; ++q) {
@@ -1388,7 +1442,7 @@ __device__ __forceinline__ void pa_update_rows(const PaOptArgs& oa,
 // ustarts/perm/seg_id walk below, as every wave does without hints.  The
 // hinted wave is a special case of the all-single branch and computes the
 // same expressions, so the results are the same bits.
-template <int Q, bool HINTS>
+template <int Q, bool HINTS, bool FTRL>
 __global__ void scatter_update_multi_kernel(
     ull* __restrict__ table_keys, unsigned* __restrict__ ticks,
     float* __restrict__ arena, const ull* __restrict__ uniq,
@@ -1452,7 +1506,7 @@ __global__ void scatter_update_multi_kernel(
             if (c < dim) graw[q][t] = g[c];
           }
         }
-        pa_load_rows<Q, T>(rows, oa, ok, rowk, dim, lane);
+        pa_load_rows<Q, T, FTRL>(rows, oa, ok, rowk, dim, lane);
         if (__ballot(kv == k) == ~0ull) {
           hinted = true;
           // the all-single expressions below, bit for bit
@@ -1549,10 +1603,10 @@ __global__ void scatter_update_multi_kernel(
     if (!any_ok) continue;
     if constexpr (HINTS) {
       // the rows of all Q keys are loaded before the dependent math
-      if (!hinted) pa_load_rows<Q, T>(rows, oa, ok, rowk, dim, lane);
-      pa_step_rows<Q, T>(rows, oa, ok, rowk, acc, dim, lane);
+      if (!hinted) pa_load_rows<Q, T, FTRL>(rows, oa, ok, rowk, dim, lane);
+      pa_step_rows<Q, T, FTRL>(rows, oa, ok, rowk, acc, dim, lane);
     } else {
-      pa_update_rows<Q, T>(oa, ok, rowk, acc, dim, lane);
+      pa_update_rows<Q, T, FTRL>(oa, ok, rowk, acc, dim, lane);
     }
   }
 }
@@ -2044,12 +2098,17 @@ void store_update(torch::Tensor table_keys, torch::Tensor ticks,
                   std::vector<double> params, double b1_power,
                   double b2_power, double weight_bound,
                   torch::Tensor skipped /* persistent i32[2]: miss, nan */) {
+  TORCH_CHECK(opt >= 0 && opt <= 3, "store_update: unknown optimizer code ",
+              opt, " (0 SGD, 1 Adagrad, 2 Adam, 3 FTRL)");
   const int64_t n = query.numel();
   if (n == 0) return;
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)arena.size(1);
+  TORCH_CHECK(opt < 2 || row_width >= 3 * dim,
+              "store_update: Adam/FTRL rows hold 3*dim floats");
   hipStream_t st = cur_stream();
-  hipLaunchKernelGGL(update_kernel, dim3(n_blocks_for(n, 4)), dim3(256), 0, st,
+  auto kernel = opt == 3 ? update_kernel<true> : update_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(n_blocks_for(n, 4)), dim3(256), 0, st,
                      (ull*)table_keys.data_ptr<int64_t>(),
                      (unsigned*)ticks.data_ptr<int32_t>(),
                      arena.data_ptr<float>(),
@@ -2179,6 +2238,8 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
                     double b2_power, double weight_bound,
                     torch::Tensor skipped, torch::Tensor u_count,
                     torch::Tensor slot_hint, torch::Tensor src_hint) {
+  TORCH_CHECK(opt >= 0 && opt <= 3, "scatter_update: unknown optimizer code ",
+              opt, " (0 SGD, 1 Adagrad, 2 Adam, 3 FTRL)");
   const int64_t n = uniq.numel();
   if (n == 0) return;
   TORCH_CHECK(grads.scalar_type() == torch::kFloat16, "scatter_update: f16 grads");
@@ -2203,7 +2264,9 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
       hints ? (const long long*)src_hint.data_ptr<int64_t>() : nullptr;
   const int64_t n_buckets = table_keys.numel() / PA_BUCKET_SIZE;
   const int row_width = (int)arena.size(1);
-  // the three variants share one signature: launch `kernel` with one wave
+  TORCH_CHECK(opt < 2 || row_width >= 3 * dim,
+              "scatter_update: Adam/FTRL rows hold 3*dim floats");
+  // the variants share one signature: launch `kernel` with one wave
   // per `keys_per_wave` unique keys
   auto launch = [&](auto kernel, int keys_per_wave) {
     const int64_t waves = (n + keys_per_wave - 1) / keys_per_wave;
@@ -2227,16 +2290,27 @@ void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
   // gradient allows (memory-level parallelism), down to one above 256
   const bool packed_small = (dim < PA_WAVE && (PA_WAVE % dim) == 0);
   // the hinted code is a separate instantiation: holding loaded rows across
-  // the verify costs registers, which callers without hints do not pay
+  // the verify costs registers, which callers without hints do not pay.  So
+  // is FTRL (opt 3), whose arm cost the other optimizers a wave per SIMD.
+  auto pick = [&](auto plain, auto hinted, auto ftrl, auto ftrl_hinted,
+                  int keys_per_wave) {
+    if (opt == 3) launch(hints ? ftrl_hinted : ftrl, keys_per_wave);
+    else launch(hints ? hinted : plain, keys_per_wave);
+  };
   if (!packed_small && dim <= 128) {
-    if (hints) launch(scatter_update_multi_kernel<4, true>, 4);
-    else launch(scatter_update_multi_kernel<4, false>, 4);
+    pick(scatter_update_multi_kernel<4, false, false>,
+         scatter_update_multi_kernel<4, true, false>,
+         scatter_update_multi_kernel<4, false, true>,
+         scatter_update_multi_kernel<4, true, true>, 4);
   } else if (!packed_small && dim <= 256) {
-    if (hints) launch(scatter_update_multi_kernel<2, true>, 2);
-    else launch(scatter_update_multi_kernel<2, false>, 2);
+    pick(scatter_update_multi_kernel<2, false, false>,
+         scatter_update_multi_kernel<2, true, false>,
+         scatter_update_multi_kernel<2, false, true>,
+         scatter_update_multi_kernel<2, true, true>, 2);
   } else {
-    if (hints) launch(scatter_update_kernel<true>, 1);
-    else launch(scatter_update_kernel<false>, 1);
+    pick(scatter_update_kernel<false, false>, scatter_update_kernel<true, false>,
+         scatter_update_kernel<false, true>, scatter_update_kernel<true, true>,
+         1);
   }
 }
 

@@ -9,6 +9,7 @@
 // kernel inlines the same expression tree.  Where a sum has two products the
 // fused one is written out (pa_adagrad_acc, pa_adam_m, pa_adam_v): which one
 // the compiler contracts is otherwise its choice, per kernel and per column.
+// FTRL (pa_ftrl, not in the reference) spells out every fma it has.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,11 +28,14 @@ __device__ __forceinline__ float pa_to_float(__hip_bfloat16 x) {
 // opt: 0 = SGD      p0=lr p1=weight_decay
 //      1 = Adagrad  p0=lr p1=g_square_momentum p2=eps p3=vectorwise_shared
 //      2 = Adam     p0=lr p1=beta1 p2=beta2 p3=eps      (store.py _opt_params)
+//      3 = FTRL     p0=lr p1=beta p2=l1 p3=l2
+// The launchers reject any other code; no kernel has a default arm.
 struct PaOptArgs {
   int opt;
   float p0, p1, p2, p3;
   float weight_bound;
   float om1, om2, c1, c2;  // Adam: 1-beta, 1/(1-beta^t)
+  float ilr;               // FTRL: 1/lr
 };
 
 __device__ __forceinline__ PaOptArgs pa_opt_args(int opt, float p0, float p1,
@@ -46,6 +50,7 @@ __device__ __forceinline__ PaOptArgs pa_opt_args(int opt, float p0, float p1,
   a.om2 = 1.0f - p2;
   a.c1 = 1.0f / (1.0f - b1_power);
   a.c2 = 1.0f / (1.0f - b2_power);
+  a.ilr = 1.0f / p0;
   return a;
 }
 
@@ -112,6 +117,44 @@ __device__ __forceinline__ float pa_adam_v(const PaOptArgs& a, float v, float g)
 __device__ __forceinline__ float pa_adam_w(const PaOptArgs& a, float w, float m,
                                            float v) {
   return pa_clamp_weight(a, w - a.p0 * (m * a.c1) / (a.p3 + sqrtf(v * a.c2)));
+}
+
+// FTRL-Proximal, per coordinate (McMahan et al. 2013, "Ad Click Prediction",
+// Algorithm 1); row = [w | z | n], z where Adam keeps m and n where it keeps v:
+//   n1    = n + g*g
+//   sigma = (sqrt(n1) - sqrt(n)) / lr
+//   z1    = z + (g - sigma*w)
+//   w1    = (clip(z1, -l1, +l1) - z1) / ((beta + sqrt(n1))/lr + l2)
+// The new weight is a function of (z1, n1) alone, exactly 0 where |z1| <= l1;
+// the old weight enters only through sigma*w.  The divisions by lr are
+// products with the rounded reciprocal a.ilr.  Every sum that takes a product
+// is a spelled-out fma, and there is one expression tree for every kernel:
+// s0 = sqrtf(n) and s1 = sqrtf(n1) are computed once in pa_ftrl and shared.
+__device__ __forceinline__ float pa_ftrl_n(float n, float g) {
+  return __builtin_fmaf(g, g, n);
+}
+__device__ __forceinline__ float pa_ftrl_z(const PaOptArgs& a, float w, float z,
+                                           float s0, float s1, float g) {
+  const float sigma = (s1 - s0) * a.ilr;
+  return z + __builtin_fmaf(-sigma, w, g);
+}
+__device__ __forceinline__ float pa_ftrl_w(const PaOptArgs& a, float z1,
+                                           float s1) {
+  const float q = __builtin_fmaf(a.p1 + s1, a.ilr, a.p3);
+  const float clip = fminf(fmaxf(z1, -a.p2), a.p2);
+  return pa_clamp_weight(a, (clip - z1) / q);
+}
+struct PaFtrlRow {
+  float w, z, n;
+};
+__device__ __forceinline__ PaFtrlRow pa_ftrl(const PaOptArgs& a, float w,
+                                             float z, float n, float g) {
+  PaFtrlRow r;
+  r.n = pa_ftrl_n(n, g);
+  const float s1 = sqrtf(r.n);
+  r.z = pa_ftrl_z(a, w, z, sqrtf(n), s1, g);
+  r.w = pa_ftrl_w(a, r.z, s1);
+  return r;
 }
 
 // Ordered gradient reduction of one unique key: accumulate its positions

@@ -13,6 +13,8 @@ Update math is identical to the reference AVX2 kernels
   note the accumulator read happens *before* its update)
 * Adam:     bias-corrected with per-feature-group β-power accumulators
   (persia-common/src/optim.rs:147-216)
+
+Beyond the reference: ``Ftrl``, per-coordinate FTRL-Proximal with L1/L2.
 """
 from abc import ABC
 from typing import Tuple
@@ -106,3 +108,54 @@ class Adagrad(Optimizer):
 
     def state_init(self, dim: int) -> float:
         return self.initial_accumulator_value
+
+
+class Ftrl(Optimizer):
+    """Per-coordinate FTRL-Proximal with L1 and L2 (McMahan et al. 2013, "Ad
+    Click Prediction", Algorithm 1).  Not part of the reference API.
+
+    The row is ``[w | z | n]``: ``z`` where Adam keeps ``m``, ``n`` where it
+    keeps ``v``, both starting at 0.  One step on a reduced gradient ``g``::
+
+        n1    = n + g*g
+        sigma = (sqrt(n1) - sqrt(n)) / lr
+        z1    = z + (g - sigma*w)
+        w1    = (clip(z1, -l1, +l1) - z1) / ((beta + sqrt(n1))/lr + l2)
+
+    so a weight whose ``|z1| <= l1`` is exactly 0: this is what makes the
+    table sparse.  The weight bound, the NaN-row skip and the miss counter
+    behave as for the other optimizers.
+
+    Two consequences of the weight being a function of ``(z, n)``:
+
+    * A seeded non-zero init is not a fixed point.  The previous weight
+      enters a step only through ``sigma*w``; even a zero-gradient update
+      rewrites ``w`` from ``(z, n)``, which for a fresh row is 0.  Textbook
+      FTRL wants ``emb_initialization`` at or near 0.
+    * A checkpoint written with Ftrl has Adam's row width (``3*dim``) and
+      the file format does not record the optimizer, so loading an Adam
+      checkpoint into an Ftrl engine, or the other way round, is not
+      detected: the moments would be read as ``z`` and ``n``.
+    """
+
+    kind = "ftrl"
+
+    def __init__(self, lr: float = 0.05, beta: float = 1.0, l1: float = 0.0,
+                 l2: float = 0.0):
+        # beta > 0 keeps the divisor (beta + sqrt(n))/lr + l2 away from 0
+        # from any state
+        if not lr > 0:
+            raise ValueError(f"Ftrl: lr must be > 0, got {lr}")
+        if not beta > 0:
+            raise ValueError(f"Ftrl: beta must be > 0, got {beta}")
+        if not l1 >= 0:
+            raise ValueError(f"Ftrl: l1 must be >= 0, got {l1}")
+        if not l2 >= 0:
+            raise ValueError(f"Ftrl: l2 must be >= 0, got {l2}")
+        self.lr = lr
+        self.beta = beta
+        self.l1 = l1
+        self.l2 = l2
+
+    def require_space(self, dim: int) -> int:
+        return 2 * dim

@@ -172,3 +172,30 @@ def adam_update(
     emb -= lr * m_hat / (eps + v_hat.sqrt())
     if weight_bound > 0:
         emb.clamp_(-weight_bound, weight_bound)
+
+
+def ftrl_update(
+    emb: torch.Tensor,  # [n, dim] f32
+    z: torch.Tensor,  # [n, dim] f32
+    n: torch.Tensor,  # [n, dim] f32
+    grad: torch.Tensor,  # [n, dim] f32
+    lr: float,
+    beta: float,
+    l1: float,
+    l2: float,
+    weight_bound: float,
+) -> None:
+    """Per-coordinate FTRL-Proximal (McMahan et al. 2013, Algorithm 1; not in
+    the reference): n += g²; z += g - sigma*w with sigma = (sqrt(n_new) -
+    sqrt(n_old))/lr; w = (clip(z, ±l1) - z) / ((beta + sqrt(n_new))/lr + l2),
+    which is exactly 0 where |z| <= l1.  The old weight enters only through
+    sigma*w (csrc/optim.h pa_ftrl)."""
+    s0 = n.sqrt()
+    n.add_(grad * grad)
+    s1 = n.sqrt()
+    sigma = (s1 - s0) / lr
+    z.add_(grad - sigma * emb)
+    q = (beta + s1) / lr + l2
+    emb.copy_((z.clamp(-l1, l1) - z) / q)
+    if weight_bound > 0:
+        emb.clamp_(-weight_bound, weight_bound)

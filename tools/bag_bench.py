@@ -16,7 +16,11 @@ per engine: the median ms/step and its min/max over the repetitions, and the
 producer-thread time per batch (PA_PROD_TIMING: host time inside
 ``process_batch``).  One JSON line.
 
+``--optimizer`` picks the embedding optimizer (default adagrad); adam and ftrl
+move three vectors per column where adagrad moves two.
+
 Run: python tools/bag_bench.py [--steps 200] [--reps 3]
+         [--optimizer {sgd,adagrad,adam,ftrl}]
 """
 import argparse
 import json
@@ -35,7 +39,7 @@ from persia_amd.embedding import EmbeddingConfig
 from persia_amd.embedding.data import (
     IDTypeFeatureWithSingleID, Label, PersiaBatch, _FlatIDFeature,
 )
-from persia_amd.embedding.optim import Adagrad
+from persia_amd.embedding import optim
 
 
 def make_batch(seed, n_slots, B, vocab, mean_len, max_len):
@@ -60,7 +64,17 @@ def make_batch(seed, n_slots, B, vocab, mean_len, max_len):
     return batch
 
 
-def make_engine(bag_fast, n_slots, dim, capacity, device):
+def make_optimizer(name):
+    if name == "sgd":
+        return optim.SGD(lr=0.01)
+    if name == "adagrad":
+        return optim.Adagrad(lr=0.01)
+    if name == "adam":
+        return optim.Adam(lr=0.001)
+    return optim.Ftrl(lr=0.05, beta=1.0, l1=1e-4, l2=1e-4)
+
+
+def make_engine(bag_fast, n_slots, dim, capacity, device, optimizer="adagrad"):
     os.environ["PA_BAG_FAST"] = "1" if bag_fast else "0"
     os.environ["PA_PROD_TIMING"] = "1"
     schema = EmbeddingSchema(
@@ -69,7 +83,8 @@ def make_engine(bag_fast, n_slots, dim, capacity, device):
         feature_index_prefix_bit=8,
     )
     eng = EmbeddingEngine(
-        schema=schema, hyper=EmbeddingConfig(), optimizer=Adagrad(lr=0.01),
+        schema=schema, hyper=EmbeddingConfig(),
+        optimizer=make_optimizer(optimizer),
         gconf=GlobalConfig(capacity=capacity), device=device,
         dist_ctx=DistContext(1, 0),
     )
@@ -101,6 +116,8 @@ def main():
     ap.add_argument("--vocab", type=int, default=1_000_000)
     ap.add_argument("--pool", type=int, default=8)
     ap.add_argument("--capacity", type=int, default=1 << 23)
+    ap.add_argument("--optimizer", default="adagrad",
+                    choices=["sgd", "adagrad", "adam", "ftrl"])
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
@@ -111,8 +128,9 @@ def main():
                       dtype=torch.float16, device=device)
     engines = {
         "generic": make_engine(False, args.slots, args.dim, args.capacity,
-                               device),
-        "bag": make_engine(True, args.slots, args.dim, args.capacity, device),
+                               device, args.optimizer),
+        "bag": make_engine(True, args.slots, args.dim, args.capacity, device,
+                           args.optimizer),
     }
     for eng in engines.values():
         run(eng, pool, grad, len(pool))  # warm-up: one pass over the pool
@@ -126,7 +144,8 @@ def main():
     out = {
         "shape": dict(slots=args.slots, dim=args.dim, batch=args.batch,
                       vocab=args.vocab, mean_nnz=int(np.mean(nnz)),
-                      steps=args.steps, reps=args.reps),
+                      steps=args.steps, reps=args.reps,
+                      optimizer=args.optimizer),
         "bag_path_taken": bool(getattr(engines["bag"], "_bag_fast", False)),
     }
     for name in engines:
