@@ -135,6 +135,7 @@ class DLRM(nn.Module):
         super().__init__()
         self.dim = dim
         self.num_sparse = num_sparse
+        self.fused = fused
         n_f = num_sparse + 1
         inter_out = n_f * (n_f - 1) // 2
         if fused:
@@ -178,9 +179,11 @@ class DLRM(nn.Module):
                     # K%128 by catting the zero tail here — one cat pass
                     # instead of cat + a full-width _pad32 copy inside the
                     # first top layer (zero K-columns hit zero-padded weight
-                    # columns: bit-identical output)
+                    # columns: bit-identical output).  Only the fused top
+                    # takes a wider input; an eager nn.Linear top would
+                    # reject it
                     k = x.shape[1] + inter.shape[1]
-                    pad = (-k) % 128
+                    pad = (-k) % 128 if self.fused else 0
                     parts = [x, inter]
                     if pad:
                         parts.append(x.new_zeros(B, pad))
