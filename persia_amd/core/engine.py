@@ -164,6 +164,23 @@ def pack_bag_buffer(feats, alloc=None) -> Tuple[np.ndarray, int, int]:
     every slot has the same B, and its offsets start at 0, never decrease
     and end at ``len(values)``."""
     S = len(feats)
+    B = _check_bag_offsets(feats)
+    lens = [len(f.values) for f in feats]
+    nnz = int(sum(lens))
+    total = nnz + (S + 1) + S * (B + 1)
+    buf = np.empty(total, dtype=np.int64) if alloc is None else alloc(total)
+    pos = 0
+    for f, n in zip(feats, lens):
+        buf[pos : pos + n] = np.asarray(f.values, dtype=np.uint64).view(np.int64)
+        pos += n
+    buf[nnz] = 0
+    np.cumsum(lens, out=buf[nnz + 1 : nnz + S + 1])
+    buf[nnz + S + 1 :].reshape(S, B + 1)[:] = [f.offsets for f in feats]
+    return buf, nnz, B
+
+
+def _check_bag_offsets(feats) -> int:
+    """pack_bag_buffer's checks of every slot's offsets -> B."""
     B = len(feats[0].offsets) - 1
     for f in feats:
         offs = np.asarray(f.offsets)
@@ -180,18 +197,78 @@ def pack_bag_buffer(feats, alloc=None) -> Tuple[np.ndarray, int, int]:
                 f"slot {f.name}: offsets end at {offs[-1]}, "
                 f"the slot has {len(f.values)} ids"
             )
+    return B
+
+
+def pack_stack_bag_buffer(
+    feats, rounds, sizes, alloc=None
+) -> Tuple[np.ndarray, int, int, int]:
+    """The host staging buffer of a bag group with hashstack slots.  Slot s
+    has ``rounds[s]`` hashstack rounds (0: none) over ``sizes[s]`` buckets
+    (its ``embedding_size``); each of its ids becomes ``rounds[s]`` positions
+    inside its sample's span, so the slot's offsets grow by that factor.  One
+    i64 array
+
+        values[nnz_in] ‖ slot_starts[S+1] ‖ offsets[S, B+1] ‖ in_starts[S+1]
+
+    ``values`` are the ids as they came: the expansion and the hashing run on
+    the device (sign_prep_bags).  ``slot_starts`` and ``offsets`` are in the
+    expanded position space (a stacked slot's offsets times its rounds,
+    relative to the slot's start), so ``slot_starts ‖ offsets`` is the plan
+    of pack_bag_buffer over ``nnz_out`` positions; ``in_starts`` are the
+    slots' starts in ``values``.  -> (buffer, nnz_in, nnz_out, B).
+
+    The offsets are checked as pack_bag_buffer checks them.  ValueError also
+    for a negative round count and for a stacked slot of fewer than one
+    bucket.  Without a stacked slot the buffer is pack_bag_buffer's, byte for
+    byte, and nnz_out == nnz_in."""
+    S = len(feats)
+    if len(rounds) != S or len(sizes) != S:
+        raise ValueError(
+            f"{S} slots, {len(rounds)} round counts and {len(sizes)} sizes"
+        )
+    for f, r, size in zip(feats, rounds, sizes):
+        if r < 0:
+            raise ValueError(f"slot {f.name}: {r} hashstack rounds")
+        if r > 0 and size < 1:
+            raise ValueError(
+                f"slot {f.name}: hashstack embedding_size {size}, below 1"
+            )
+    if not any(rounds):
+        buf, nnz, B = pack_bag_buffer(feats, alloc)
+        return buf, nnz, nnz, B
+    B = _check_bag_offsets(feats)
     lens = [len(f.values) for f in feats]
-    nnz = int(sum(lens))
-    total = nnz + (S + 1) + S * (B + 1)
+    grow = [max(int(r), 1) for r in rounds]
+    nnz_in = int(sum(lens))
+    nnz_out = int(sum(n * g for n, g in zip(lens, grow)))
+    total = nnz_in + 2 * (S + 1) + S * (B + 1)
     buf = np.empty(total, dtype=np.int64) if alloc is None else alloc(total)
     pos = 0
     for f, n in zip(feats, lens):
         buf[pos : pos + n] = np.asarray(f.values, dtype=np.uint64).view(np.int64)
         pos += n
-    buf[nnz] = 0
-    np.cumsum(lens, out=buf[nnz + 1 : nnz + S + 1])
-    buf[nnz + S + 1 :].reshape(S, B + 1)[:] = [f.offsets for f in feats]
-    return buf, nnz, B
+    starts = buf[nnz_in : nnz_in + S + 1]
+    starts[0] = 0
+    np.cumsum([n * g for n, g in zip(lens, grow)], out=starts[1:])
+    offs = buf[nnz_in + S + 1 : total - (S + 1)].reshape(S, B + 1)
+    for s, (f, g) in enumerate(zip(feats, grow)):
+        offs[s] = np.asarray(f.offsets, dtype=np.int64) * g
+    in_starts = buf[total - (S + 1) :]
+    in_starts[0] = 0
+    np.cumsum(lens, out=in_starts[1:])
+    return buf, nnz_in, nnz_out, B
+
+
+def _stack_config(cfgs) -> Tuple[List[int], List[int]]:
+    """Per slot: hashstack rounds (0: none) and the bucket count of a stacked
+    slot (1 elsewhere, as _group_keys passes it)."""
+    rounds = [int(c.hash_stack_rounds) for c in cfgs]
+    sizes = [
+        int(c.hash_stack_config.embedding_size) if r > 0 else 1
+        for c, r in zip(cfgs, rounds)
+    ]
+    return rounds, sizes
 
 
 def raw_slot_meta(S: int, B: int, sfs: List[int]) -> np.ndarray:
@@ -317,13 +394,25 @@ class _GroupPlan:
 class _BagPlan:
     """Static per-(group, batch-size) device constants of the bag path (sum
     slots with any number of ids per sample).  The positions vary per batch
-    and come with the upload; only what the slot configs fix lives here."""
+    and come with the upload; only what the slot configs fix lives here.
+    ``rounds`` / ``sizes`` are the slots' hashstack rounds (0: none) and
+    bucket counts on the host, ``stack_dev`` the same as device tensors for
+    the sign-prep kernel; all three None for a group without a stacked
+    slot."""
 
     def __init__(self, dim: int, cfgs: List[SlotConfig], B: int,
                  device: torch.device):
         self.dim = dim
         self.B = B
         self.S = len(cfgs)
+        self.rounds = self.sizes = self.stack_dev = None
+        rounds, sizes = _stack_config(cfgs)
+        if any(rounds):
+            self.rounds, self.sizes = rounds, sizes
+            self.stack_dev = (
+                torch.tensor(rounds, dtype=torch.int32, device=device),
+                torch.tensor(sizes, dtype=torch.int64, device=device),
+            )
         prefixes_np = np.array([c.index_prefix for c in cfgs], dtype=np.uint64)
         self.prefixes = torch.from_numpy(prefixes_np.view(np.int64)).to(device)
         sqrt = [bool(c.sqrt_scaling) for c in cfgs]
@@ -583,8 +672,9 @@ class EmbeddingEngine:
         # same results)
         self._update_hints = os.environ.get("PA_UPDATE_HINTS", "1") != "0"
         # PA_BAG_FAST (default on): single-GPU dim-groups of sum slots with
-        # several ids per sample take the one-call native bag lookup; 0 sends
-        # them down the generic path (A/B switch, same results)
+        # several ids per sample or with hashstack rounds take the one-call
+        # native bag lookup; 0 sends them down the generic path (A/B switch,
+        # same results)
         self._bag_fast = os.environ.get("PA_BAG_FAST", "1") != "0"
         # PA_RAW_FAST (default on): single-GPU dim-groups with raw (sequence)
         # slots and no hashstack take the one-call native raw lookup; 0 sends
@@ -994,7 +1084,7 @@ class EmbeddingEngine:
                 if dim not in pc:
                     pc[dim] = self._pin_values(feats)
             elif self._bag_group(dim, feats):
-                self._bag_host_buffer(batch, dim, feats)
+                self._stack_host_buffer(batch, dim, feats)
             elif self._raw_group(dim, feats):
                 self._bag_host_buffer(
                     batch, dim, self._sums_first(feats), kind="raw"
@@ -1062,17 +1152,24 @@ class EmbeddingEngine:
 
     def _bag_group(self, dim: int, feats) -> bool:
         """The bag-path shape: a single-GPU native group (the one-call
-        condition of _process_group_fast) of sum slots without hashstack, at
-        least one of them with several ids per sample, and PA_BAG_FAST on.
-        All-single-ID groups keep their own path and its static plan."""
+        condition of _process_group_fast) of sum slots, at least one of them
+        with several ids per sample or with hashstack rounds (each id of such
+        a slot becomes ``rounds`` positions: a bag even when the feature
+        carries one id per sample), and PA_BAG_FAST on.  All-single-ID groups
+        without a stacked slot keep their own path and its static plan; a
+        group with a raw slot is never a bag group."""
         if not (self._bag_fast and self._one_call(dim)):
             return False
         get_slot = self.schema.get_slot
+        stacked = False
         for f in feats:
             cfg = get_slot(f.name)
-            if not cfg.embedding_summation or cfg.hash_stack_rounds != 0:
+            if not cfg.embedding_summation or cfg.hash_stack_rounds < 0:
                 return False
-        return not all(getattr(f, "is_single", False) for f in feats)
+            stacked = stacked or cfg.hash_stack_rounds > 0
+        return stacked or not all(
+            getattr(f, "is_single", False) for f in feats
+        )
 
     def _one_call(self, dim: int) -> bool:
         """A group of this dim can be looked up in one native call: CUDA
@@ -1125,6 +1222,38 @@ class EmbeddingEngine:
 
             _buf, nnz, B = pack_bag_buffer(feats, alloc)
             hit = pc[(kind, dim)] = (made[0], nnz, B)
+        return hit
+
+    def _stack_host_buffer(self, batch, dim: int, feats):
+        """The staging buffer of a bag group that may hold hashstack slots,
+        -> (i64 tensor, nnz_in, nnz_out, B).  Without a stacked slot it is
+        _bag_host_buffer's (nnz_out == nnz_in); with one it is
+        pack_stack_bag_buffer's, built, checked and cached the same way under
+        the same ``("bag", dim)``, the two counts in the cached tuple."""
+        rounds, sizes = _stack_config(
+            [self.schema.get_slot(f.name) for f in feats]
+        )
+        if not any(rounds):
+            pin, nnz, B = self._bag_host_buffer(batch, dim, feats)
+            return pin, nnz, nnz, B
+        pc = getattr(batch, "_pinned_cache", None)
+        if pc is None:
+            pc = batch._pinned_cache = {}
+        hit = pc.get(("bag", dim))
+        if hit is None:
+            made = []
+
+            def alloc(n: int) -> np.ndarray:
+                made.append(torch.empty(
+                    n, dtype=torch.int64,
+                    pin_memory=self.device.type == "cuda",
+                ))
+                return made[0].numpy()
+
+            _buf, nnz_in, nnz_out, B = pack_stack_bag_buffer(
+                feats, rounds, sizes, alloc
+            )
+            hit = pc[("bag", dim)] = (made[0], nnz_in, nnz_out, B)
         return hit
 
     def _padded_a2a(self, store) -> bool:
@@ -1251,15 +1380,18 @@ class EmbeddingEngine:
     def _process_group_bags(self, dim: int, feats, out: PersiaTrainingBatch,
                             train: bool, batch: PersiaBatch) -> _GroupCtx:
         """Bag path: sum slots with any number of ids per sample (a single-ID
-        slot is a bag of length 1), single GPU.  One async upload of values
-        and offsets, one native call for sign prep, padded dedup, the segment
-        plan, probe/insert and the sums read straight from the arena.  No
-        host sync between the upload and the return.  The group it leaves is
-        what the generic path leaves, with the unique count on the device."""
+        slot is a bag of length 1, a slot of R hashstack rounds a bag of R
+        positions per id), single GPU.  One async upload of the unexpanded
+        values and the offsets, one native call for sign prep (with the
+        hashstack expansion), padded dedup, the segment plan, probe/insert
+        and the sums read straight from the arena.  No host sync between the
+        upload and the return.  The group it leaves is what the generic path
+        leaves, positions and offsets in the expanded space, with the unique
+        count on the device."""
         timing = self._prod_timing
         if timing:
             t0 = time.perf_counter()
-        pin, nnz, B = self._bag_host_buffer(batch, dim, feats)
+        pin, nnz_in, nnz, B = self._stack_host_buffer(batch, dim, feats)
         names = tuple(f.name for f in feats)
         plan = self._plans.get(("bag", dim, names, B))
         if plan is None:
@@ -1274,13 +1406,17 @@ class EmbeddingEngine:
          cat_offsets, seg_id, seg_lens, fwd_scale) = self.stores[
             dim
         ].lookup_local_bags(
-            upload, nnz, S, B, plan.prefixes, self._spacing_arg,
+            upload, nnz_in, S, B, plan.prefixes, self._spacing_arg,
             plan.sqrt_flags, train and self._update_hints, train,
+            rounds=plan.rounds, sizes=plan.sizes, nnz_out=nnz,
+            stack_dev=plan.stack_dev,
         )
         # per-slot views of the upload: positions on the host, offsets on
-        # the device
-        starts = pin.numpy()[nnz : nnz + S + 1]
-        offsets = upload[nnz + S + 1 :].view(S, B + 1)
+        # the device (both in the expanded space of a stacked group)
+        starts = pin.numpy()[nnz_in : nnz_in + S + 1]
+        offsets = upload[
+            nnz_in + S + 1 : nnz_in + S + 1 + S * (B + 1)
+        ].view(S, B + 1)
         slot_ctxs = [
             _SlotCtx(
                 name=f.name, cfg=self.schema.get_slot(f.name),

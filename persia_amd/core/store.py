@@ -762,7 +762,9 @@ class HipEmbeddingStore(EmbeddingStoreBase):
 
     def lookup_local_bags(self, upload: torch.Tensor, nnz: int, S: int,
                           B: int, prefixes: torch.Tensor, spacing_arg: int,
-                          sqrt_flags: torch.Tensor, hints: bool, train: bool):
+                          sqrt_flags: torch.Tensor, hints: bool, train: bool,
+                          rounds=None, sizes=None, nnz_out: Optional[int] = None,
+                          stack_dev=None):
         """The whole single-GPU lookup of a bag group (sum slots with any
         number of ids per sample) in one native call.  ``upload`` is the
         group's device buffer ``values[nnz] ‖ slot_starts[S+1] ‖
@@ -772,9 +774,46 @@ class HipEmbeddingStore(EmbeddingStoreBase):
         cat_offsets, seg_id, seg_lens, seg_scale): ``lookup_local``'s results
         and the group's segment plan.  ``seg_scale`` is empty (all ones)
         without a sqrt slot; the hints are empty unless ``hints`` and
-        ``train``."""
-        return self._C.lookup_local_bags(
-            upload, nnz, S, B, prefixes, spacing_arg, sqrt_flags, int(hints),
+        ``train``.
+
+        A group with hashstack slots passes ``rounds`` and ``sizes`` (host
+        sequences of S ints: the slots' ``hash_stack_rounds``, 0 for none,
+        and ``embedding_size``) and ``nnz_out``, the number of expanded
+        positions.  ``upload`` is then engine ``pack_stack_bag_buffer``'s,
+        ``values[nnz] ‖ slot_starts[S+1] ‖ offsets[S, B+1] ‖ in_starts[S+1]``
+        with the ids unexpanded and the plan in the expanded space, and the
+        results are sized by ``nnz_out``.  ``stack_dev`` is the pair of device
+        tensors (rounds i32[S], sizes i64[S]) of the same values, which a
+        caller with a static plan builds once; without it they are uploaded
+        here.  Everything is checked on the host, before any launch."""
+        if rounds is None:
+            return self._C.lookup_local_bags(
+                upload, nnz, S, B, prefixes, spacing_arg, sqrt_flags,
+                int(hints), self.keys, self.ticks, self.arena,
+                *self._lookup_args(train, self.next_tick()),
+            )
+        rounds, sizes = [int(r) for r in rounds], [int(z) for z in sizes]
+        if len(rounds) != S or len(sizes) != S:
+            raise ValueError(
+                f"lookup_local_bags: {S} slots, {len(rounds)} round counts "
+                f"and {len(sizes)} sizes"
+            )
+        if nnz_out is None:
+            raise ValueError("lookup_local_bags: rounds without nnz_out")
+        if not any(r > 1 for r in rounds) and nnz_out != nnz:
+            # no slot expands: the position count is the id count
+            raise ValueError(
+                f"lookup_local_bags: {nnz_out} positions from {nnz} ids, "
+                f"no slot has more than one round"
+            )
+        if stack_dev is None:
+            stack_dev = (
+                torch.tensor(rounds, dtype=torch.int32, device=upload.device),
+                torch.tensor(sizes, dtype=torch.int64, device=upload.device),
+            )
+        return self._C.lookup_local_bags_stack(
+            upload, nnz, nnz_out, S, B, prefixes, spacing_arg, sqrt_flags,
+            stack_dev[0], stack_dev[1], rounds, sizes, int(hints),
             self.keys, self.ticks, self.arena,
             *self._lookup_args(train, self.next_tick()),
         )

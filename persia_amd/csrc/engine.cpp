@@ -58,6 +58,10 @@ void grad_scatter(torch::Tensor grads, torch::Tensor perm,
                   int64_t accumulate);
 torch::Tensor sign_prep(torch::Tensor values, torch::Tensor slot_starts,
                         torch::Tensor prefixes, int64_t spacing);
+torch::Tensor sign_prep_bags(torch::Tensor upload, int64_t nnz_in,
+                             int64_t nnz_out, int64_t S, int64_t B,
+                             torch::Tensor prefixes, torch::Tensor rounds,
+                             torch::Tensor sizes, int64_t spacing);
 void scatter_update(torch::Tensor table_keys, torch::Tensor ticks,
                     torch::Tensor arena, torch::Tensor uniq,
                     torch::Tensor grads, torch::Tensor perm,
@@ -165,6 +169,36 @@ std::vector<torch::Tensor> lookup_local(
   return {sums, uniq, inverse, perm, ustarts, u_count, hints[0], hints[1]};
 }
 
+// The bag lookup behind sign prep: padded dedup -> segment plan ->
+// probe/claim -> init launch (training) -> sums straight from the arena.
+// `plan` is slot_starts[S+1] ‖ offsets[S, B+1] over the keys' positions.
+static std::vector<torch::Tensor> bags_from_keys(
+    torch::Tensor keys, torch::Tensor plan, int64_t S, int64_t B,
+    torch::Tensor sqrt_flags, int64_t hints, torch::Tensor table_keys,
+    torch::Tensor ticks, torch::Tensor arena, int64_t dim, int64_t train,
+    int64_t tick, double lo, double hi, double admit_prob, double state_init,
+    int64_t opt_space) {
+  auto d = dedup_padded(keys);
+  auto& uniq = d[0];
+  auto& inverse = d[1];
+  auto& perm = d[2];
+  auto& ustarts = d[3];
+  auto& u_count = d[4];
+  auto p = bag_plan(plan, S, B, keys.numel(), sqrt_flags);
+  auto& cat_offsets = p[0];
+  auto& seg_id = p[1];
+  auto sums = torch::empty(
+      {S * B, dim},
+      torch::TensorOptions().dtype(torch::kFloat16).device(keys.device()));
+  const bool want_hints = train && hints;
+  auto h = store_lookup_bags(
+      table_keys, ticks, arena, uniq, inverse, perm, ustarts, cat_offsets,
+      p[3], sums, dim, train, tick, lo, hi, admit_prob, state_init, opt_space,
+      u_count, want_hints ? seg_id : seg_id.narrow(0, 0, 0));
+  return {sums,       uniq, inverse,     perm,   ustarts, u_count,
+          h[0],       h[1], cat_offsets, seg_id, p[2],    p[3]};
+}
+
 // Single-GPU fused lookup of a bag group: sum slots with any number of ids per
 // sample.  `upload` is the group's one H2D buffer,
 //   values[nnz] ‖ slot_starts[S+1] ‖ offsets[S, B+1]
@@ -198,25 +232,66 @@ std::vector<torch::Tensor> lookup_local_bags(
   auto slot_starts = upload.narrow(0, nnz, S + 1);
   auto plan = upload.narrow(0, nnz, S + 1 + S * (B + 1));
   auto keys = sign_prep(values, slot_starts, prefixes, spacing);
-  auto d = dedup_padded(keys);
-  auto& uniq = d[0];
-  auto& inverse = d[1];
-  auto& perm = d[2];
-  auto& ustarts = d[3];
-  auto& u_count = d[4];
-  auto p = bag_plan(plan, S, B, nnz, sqrt_flags);
-  auto& cat_offsets = p[0];
-  auto& seg_id = p[1];
-  auto sums = torch::empty(
-      {S * B, dim},
-      torch::TensorOptions().dtype(torch::kFloat16).device(upload.device()));
-  const bool want_hints = train && hints;
-  auto h = store_lookup_bags(
-      table_keys, ticks, arena, uniq, inverse, perm, ustarts, cat_offsets,
-      p[3], sums, dim, train, tick, lo, hi, admit_prob, state_init, opt_space,
-      u_count, want_hints ? seg_id : seg_id.narrow(0, 0, 0));
-  return {sums,       uniq, inverse,     perm,   ustarts, u_count,
-          h[0],       h[1], cat_offsets, seg_id, p[2],    p[3]};
+  return bags_from_keys(keys, plan, S, B, sqrt_flags, hints, table_keys, ticks,
+                        arena, dim, train, tick, lo, hi, admit_prob, state_init,
+                        opt_space);
+}
+
+// lookup_local_bags for a group with hashstack slots (a stacked sum slot is a
+// bag: each id becomes R bucketed ids inside its sample's span).  `upload` is
+//   values[nnz_in] ‖ slot_starts[S+1] ‖ offsets[S, B+1] ‖ in_starts[S+1]
+// with slot_starts and offsets in the expanded space of nnz_out positions and
+// the ids unexpanded (engine pack_stack_bag_buffer); rounds i32[S] / sizes
+// i64[S] are the device constants of sign_prep_bags, rounds_host / sizes_host
+// the same values for the checks made here, without a sync.  Behind sign
+// prep the chain is lookup_local_bags' on nnz_out positions; the twelve
+// results are sized by nnz_out.
+std::vector<torch::Tensor> lookup_local_bags_stack(
+    torch::Tensor upload, int64_t nnz_in, int64_t nnz_out, int64_t S,
+    int64_t B, torch::Tensor prefixes, int64_t spacing,
+    torch::Tensor sqrt_flags, torch::Tensor rounds, torch::Tensor sizes,
+    std::vector<int64_t> rounds_host, std::vector<int64_t> sizes_host,
+    int64_t hints, torch::Tensor table_keys, torch::Tensor ticks,
+    torch::Tensor arena, int64_t dim, int64_t train, int64_t tick, double lo,
+    double hi, double admit_prob, double state_init, int64_t opt_space) {
+  TORCH_CHECK(S >= 1 && B >= 0 && nnz_in >= 0 && nnz_out >= 0 &&
+                  upload.scalar_type() == torch::kInt64 &&
+                  upload.is_contiguous() &&
+                  upload.numel() == nnz_in + 2 * (S + 1) + S * (B + 1),
+              "lookup_local_bags_stack: upload must be "
+              "i64[nnz_in + S+1 + S*(B+1) + S+1]");
+  TORCH_CHECK(prefixes.numel() == S,
+              "lookup_local_bags_stack: prefixes must be [S]");
+  TORCH_CHECK(rounds.numel() == S && sizes.numel() == S &&
+                  (int64_t)rounds_host.size() == S &&
+                  (int64_t)sizes_host.size() == S,
+              "lookup_local_bags_stack: rounds and sizes must be [S] (", S,
+              "), got ", rounds.numel(), ", ", sizes.numel(), ", ",
+              rounds_host.size(), ", ", sizes_host.size());
+  int64_t max_rounds = 1;
+  for (int64_t s = 0; s < S; ++s) {
+    TORCH_CHECK(rounds_host[s] >= 0, "lookup_local_bags_stack: slot ", s,
+                " has ", rounds_host[s], " hashstack rounds");
+    TORCH_CHECK(rounds_host[s] == 0 || sizes_host[s] >= 1,
+                "lookup_local_bags_stack: slot ", s, " has embedding_size ",
+                sizes_host[s]);
+    max_rounds = std::max(max_rounds, rounds_host[s]);
+  }
+  // the per-slot split of nnz_in is on the device only: hold nnz_out to what
+  // the totals allow
+  TORCH_CHECK(nnz_out >= nnz_in && nnz_out <= nnz_in * max_rounds,
+              "lookup_local_bags_stack: ", nnz_out, " positions from ", nnz_in,
+              " ids of at most ", max_rounds, " rounds");
+  // the thread-per-position limit of lookup_local_bags, on the expanded count
+  TORCH_CHECK(nnz_out <= (int64_t)16384 * 256,
+              "lookup_local_bags_stack: ", nnz_out, " positions in one "
+              "dim-group, the thread-per-position kernels cover 4194304");
+  auto plan = upload.narrow(0, nnz_in, S + 1 + S * (B + 1));
+  auto keys = sign_prep_bags(upload, nnz_in, nnz_out, S, B, prefixes, rounds,
+                             sizes, spacing);
+  return bags_from_keys(keys, plan, S, B, sqrt_flags, hints, table_keys, ticks,
+                        arena, dim, train, tick, lo, hi, admit_prob, state_init,
+                        opt_space);
 }
 
 // Single-GPU fused lookup of a raw group: S sum slots (single-ID or bags),
@@ -467,6 +542,9 @@ void init_engine(pybind11::module_& m) {
   m.def("lookup_local_bags", &lookup_local_bags,
         "fused single-GPU lookup of a multi-ID sum group (sign prep + dedup + "
         "segment plan + probe + init + sums from the arena)");
+  m.def("lookup_local_bags_stack", &lookup_local_bags_stack,
+        "lookup_local_bags for a group with hashstack slots (sign prep "
+        "expands the unexpanded ids on the device)");
   m.def("lookup_local_raw", &lookup_local_raw,
         "fused single-GPU lookup of a group with raw (sequence) slots (sign "
         "prep + dedup + plan + probe + init + sums and raw cells from the "

@@ -511,6 +511,72 @@ __global__ void sign_prep_stack_kernel(
   }
 }
 
+// sign prep of a bag group with hashstack slots, straight from the group's one
+// upload (engine pack_stack_bag_buffer):
+//   values[nnz_in] ‖ slot_starts[S+1] ‖ offsets[S, B+1] ‖ in_starts[S+1]
+// slot_starts and offsets are in the EXPANDED position space (a slot of R
+// rounds has offsets*R; they are bag_plan_kernel's `plan`), in_starts are the
+// slots' starts in `values`.  Keys and layout are sign_prep_stack_kernel's,
+// round-major inside each sample's span.  One thread per OUTPUT position q,
+// so the stores are coalesced and no thread writes R strided keys: with
+// t = q - E[b] inside sample b of expanded span [E[b], E[b+1]) and
+// len = (E[b+1] - E[b]) / R, the round is r = t / len and the id is
+// values[in_start + E[b]/R + t % len]; the thread iterates splitmix64 r+1
+// times on it (R(R+1)/2 mixes per id against R of the thread-per-id form:
+// ALU work beside two binary searches).  Slots with R == 0 take the plain
+// prefix+mix path.  The host builder has checked the offsets; rounds that
+// disagree with them give wrong keys, never a read outside `values` (len, r
+// and the id index are clamped).
+__global__ void sign_prep_bags_kernel(
+    const ull* __restrict__ values, const int64_t* __restrict__ slot_starts,
+    const int64_t* __restrict__ offsets, const int64_t* __restrict__ in_starts,
+    const ull* __restrict__ prefixes, const int* __restrict__ rounds,
+    const int64_t* __restrict__ sizes, int n_slots, int64_t B, ull spacing,
+    ull* __restrict__ out, int64_t n_in, int64_t n_out) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_out) return;
+  int lo = 0, hi = n_slots;  // slot_starts[s] <= q < slot_starts[s+1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (q >= slot_starts[mid]) lo = mid; else hi = mid;
+  }
+  const int s = lo;
+  const ull prefix = prefixes[s];
+  const int R = rounds[s];
+  const int64_t p = q - slot_starts[s];  // slot-local output position
+  int64_t src = p;
+  int r = 0;
+  if (R > 0) {
+    const int64_t* E = offsets + (int64_t)s * (B + 1);
+    int64_t blo = 0, bhi = B;  // E[blo] <= p < E[blo + 1]
+    while (bhi - blo > 1) {
+      const int64_t mid = (blo + bhi) >> 1;
+      if (p >= E[mid]) blo = mid; else bhi = mid;
+    }
+    const int64_t e0 = E[blo];
+    int64_t len = (E[blo + 1] - e0) / R;
+    if (len < 1) len = 1;
+    const int64_t t = p - e0;
+    const int64_t rr = t / len;
+    r = rr < R ? (int)rr : R - 1;
+    src = e0 / R + t % len;
+  }
+  src += in_starts[s];
+  if (src < 0) src = 0;
+  if (src >= n_in) src = n_in - 1;  // n_out > 0 implies n_in > 0
+  ull sign = values[src];
+  if (R > 0) {
+    const ull size = (ull)sizes[s];
+    ull h = sign;
+    for (int i = 0; i <= r; ++i) h = pa_splitmix64(h);
+    sign = h % size + (ull)r * size;
+  }
+  if (prefix != 0) sign = sign % spacing + prefix;
+  ull k = pa_splitmix64(sign);
+  if (k == PA_EMPTY_KEY) k = 0xD1B54A32D192ED03ull;
+  out[q] = k;
+}
+
 // ------------------------------------------------------- padded a2a routing
 // The owner partition of the SORTED uniq keys is a range partition (owner =
 // (hi32*world)>>32 is monotone in the key), so per-owner segment starts are
@@ -2393,6 +2459,50 @@ torch::Tensor sign_prep_stack(torch::Tensor values, torch::Tensor in_starts,
   return out;
 }
 
+// Sign prep of a bag group with hashstack slots (sign_prep_bags_kernel).
+// `upload` is the group's device buffer
+//   values[nnz_in] ‖ slot_starts[S+1] ‖ offsets[S, B+1] ‖ in_starts[S+1]
+// with slot_starts and offsets in the expanded position space; rounds i32[S]
+// and sizes i64[S] are the slots' hashstack rounds (0: none) and bucket
+// counts, on the device.  -> the nnz_out mixed keys.  One thread per output
+// position on the capped grid, so nnz_out is held to 16384*256 here.
+torch::Tensor sign_prep_bags(torch::Tensor upload, int64_t nnz_in,
+                             int64_t nnz_out, int64_t S, int64_t B,
+                             torch::Tensor prefixes, torch::Tensor rounds,
+                             torch::Tensor sizes, int64_t spacing) {
+  TORCH_CHECK(S >= 1 && B >= 0 && nnz_in >= 0 && nnz_out >= 0 &&
+                  upload.scalar_type() == torch::kInt64 &&
+                  upload.is_contiguous() &&
+                  upload.numel() == nnz_in + 2 * (S + 1) + S * (B + 1),
+              "sign_prep_bags: upload must be "
+              "i64[nnz_in + S+1 + S*(B+1) + S+1]");
+  TORCH_CHECK(prefixes.scalar_type() == torch::kInt64 && prefixes.numel() == S,
+              "sign_prep_bags: prefixes must be i64[S]");
+  TORCH_CHECK(rounds.scalar_type() == torch::kInt32 && rounds.numel() == S &&
+                  rounds.is_contiguous(),
+              "sign_prep_bags: rounds must be i32[S]");
+  TORCH_CHECK(sizes.scalar_type() == torch::kInt64 && sizes.numel() == S &&
+                  sizes.is_contiguous(),
+              "sign_prep_bags: sizes must be i64[S]");
+  TORCH_CHECK(nnz_out <= (int64_t)16384 * 256,
+              "sign_prep_bags: ", nnz_out, " positions in one dim-group, the "
+              "thread-per-position kernels cover 4194304");
+  TORCH_CHECK(nnz_in > 0 || nnz_out == 0,
+              "sign_prep_bags: ", nnz_out, " positions from no ids");
+  auto out = torch::empty({nnz_out}, upload.options());
+  if (nnz_out == 0) return out;
+  const int64_t* up = upload.data_ptr<int64_t>();
+  const int64_t* plan = up + nnz_in;
+  hipLaunchKernelGGL(sign_prep_bags_kernel, dim3(n_blocks_for(nnz_out, 256)),
+                     dim3(256), 0, cur_stream(), (const ull*)up, plan,
+                     plan + S + 1, plan + S + 1 + S * (B + 1),
+                     (const ull*)prefixes.data_ptr<int64_t>(),
+                     rounds.data_ptr<int32_t>(), sizes.data_ptr<int64_t>(),
+                     (int)S, B, (ull)spacing, (ull*)out.data_ptr<int64_t>(),
+                     nnz_in, nnz_out);
+  return out;
+}
+
 void init_dense(pybind11::module_& m);     // csrc/dense.hip
 void init_engine(pybind11::module_& m);    // csrc/engine.cpp
 void init_interact(pybind11::module_& m);  // csrc/interact.hip
@@ -2426,6 +2536,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sign_prep", &sign_prep, "prefix-fold + splitmix64 key mixing");
   m.def("sign_prep_stack", &sign_prep_stack,
         "hashstack expansion + prefix-fold + splitmix64 key mixing");
+  m.def("sign_prep_bags", &sign_prep_bags,
+        "sign prep of a bag group with hashstack slots, from its one upload");
   m.def("dedup_finalize", &dedup_finalize,
         "fixed-shape dedup epilogue (padded uniq/ustarts + device count)");
   m.def("sort_pairs_u64", &sort_pairs_u64, "radix sort-pairs, u64 order");

@@ -19,8 +19,13 @@ producer-thread time per batch (PA_PROD_TIMING: host time inside
 ``--optimizer`` picks the embedding optimizer (default adagrad); adam and ftrl
 move three vectors per column where adagrad moves two.
 
+``--hashstack ROUNDS:SIZE`` gives every slot a ``hash_stack_config`` of ROUNDS
+rounds over SIZE buckets (default: none), so each id becomes ROUNDS positions;
+``mean_nnz`` in the result stays the number of ids, ``mean_positions`` is the
+expanded count.
+
 Run: python tools/bag_bench.py [--steps 200] [--reps 3]
-         [--optimizer {sgd,adagrad,adam,ftrl}]
+         [--optimizer {sgd,adagrad,adam,ftrl}] [--hashstack ROUNDS:SIZE]
 """
 import argparse
 import json
@@ -34,7 +39,9 @@ import torch
 
 from persia_amd.core.comm import DistContext
 from persia_amd.core.engine import EmbeddingEngine
-from persia_amd.core.schema import EmbeddingSchema, GlobalConfig, SlotConfig
+from persia_amd.core.schema import (
+    EmbeddingSchema, GlobalConfig, HashStackConfig, SlotConfig,
+)
 from persia_amd.embedding import EmbeddingConfig
 from persia_amd.embedding.data import (
     IDTypeFeatureWithSingleID, Label, PersiaBatch, _FlatIDFeature,
@@ -74,11 +81,29 @@ def make_optimizer(name):
     return optim.Ftrl(lr=0.05, beta=1.0, l1=1e-4, l2=1e-4)
 
 
-def make_engine(bag_fast, n_slots, dim, capacity, device, optimizer="adagrad"):
+def parse_hashstack(text):
+    """"ROUNDS:SIZE" -> (rounds, size), both at least 1."""
+    rounds, _, size = text.partition(":")
+    try:
+        rounds, size = int(rounds), int(size)
+    except ValueError:
+        rounds = size = 0
+    if rounds < 1 or size < 1:
+        raise argparse.ArgumentTypeError(
+            f"{text!r}: expected ROUNDS:SIZE, two integers of at least 1")
+    return rounds, size
+
+
+def make_engine(bag_fast, n_slots, dim, capacity, device, optimizer="adagrad",
+                hashstack=None):
     os.environ["PA_BAG_FAST"] = "1" if bag_fast else "0"
     os.environ["PA_PROD_TIMING"] = "1"
+    stack = {}
+    if hashstack:
+        stack = dict(hash_stack_config=HashStackConfig(
+            hash_stack_rounds=hashstack[0], embedding_size=hashstack[1]))
     schema = EmbeddingSchema(
-        slots={f"f{i}": SlotConfig(name=f"f{i}", dim=dim)
+        slots={f"f{i}": SlotConfig(name=f"f{i}", dim=dim, **stack)
                for i in range(n_slots)},
         feature_index_prefix_bit=8,
     )
@@ -106,6 +131,15 @@ def run(eng, pool, grad, steps):
     return ev0.elapsed_time(ev1) / steps, prod * 1e3
 
 
+def path_taken(eng, batch):
+    """Whether the engine sends the batch's groups down the bag path (a tree
+    without that path has no ``_bag_group``)."""
+    if not hasattr(eng, "_bag_group"):
+        return False
+    return all(eng._bag_group(d, f)
+               for d, f in eng._feats_by_dim(batch).items())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -118,6 +152,8 @@ def main():
     ap.add_argument("--capacity", type=int, default=1 << 23)
     ap.add_argument("--optimizer", default="adagrad",
                     choices=["sgd", "adagrad", "adam", "ftrl"])
+    ap.add_argument("--hashstack", type=parse_hashstack, default=None,
+                    metavar="ROUNDS:SIZE")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
@@ -128,9 +164,9 @@ def main():
                       dtype=torch.float16, device=device)
     engines = {
         "generic": make_engine(False, args.slots, args.dim, args.capacity,
-                               device, args.optimizer),
+                               device, args.optimizer, args.hashstack),
         "bag": make_engine(True, args.slots, args.dim, args.capacity, device,
-                           args.optimizer),
+                           args.optimizer, args.hashstack),
     }
     for eng in engines.values():
         run(eng, pool, grad, len(pool))  # warm-up: one pass over the pool
@@ -146,8 +182,11 @@ def main():
                       vocab=args.vocab, mean_nnz=int(np.mean(nnz)),
                       steps=args.steps, reps=args.reps,
                       optimizer=args.optimizer),
-        "bag_path_taken": bool(getattr(engines["bag"], "_bag_fast", False)),
+        "bag_path_taken": path_taken(engines["bag"], pool[0]),
     }
+    if args.hashstack:
+        out["shape"]["hashstack"] = "%d:%d" % args.hashstack
+        out["shape"]["mean_positions"] = int(np.mean(nnz)) * args.hashstack[0]
     for name in engines:
         out[name] = dict(
             ms_per_step_median=round(statistics.median(ms[name]), 4),
