@@ -2507,12 +2507,14 @@ void init_dense(pybind11::module_& m);     // csrc/dense.hip
 void init_engine(pybind11::module_& m);    // csrc/engine.cpp
 void init_interact(pybind11::module_& m);  // csrc/interact.hip
 void init_checkpoint(pybind11::module_& m);  // csrc/checkpoint.hip
+void init_seqattn(pybind11::module_& m);   // csrc/seqattn.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "persia_amd HIP kernels (gfx950)";
   init_dense(m);
   init_engine(m);
   init_interact(m);
+  init_seqattn(m);
   init_checkpoint(m);
   m.def("store_lookup", &store_lookup, "hash-table lookup/insert + gather");
   m.def("store_probe", &store_probe, "probe-only (spill-tier miss detection)");

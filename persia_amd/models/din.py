@@ -1,0 +1,88 @@
+"""Sequence CTR model with DIN-style target attention over raw slots.
+
+A raw (sequence) slot arrives as ``(B, sample_fixed_size, dim+1)`` with the
+0/1 mask as the last channel; ``TargetAttentionPool`` reduces it to ``(B,
+dim)`` with the candidate item's embedding (a sum slot of the same dim) as
+the query — scaled dot-product scores, softmax over the valid cells, weighted
+sum of the rows (ops/seqattn.py: one HIP kernel per direction on the GPU, the
+torch reference on CPU)."""
+from typing import Dict, List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from persia_amd.ops.seqattn import seq_attn_pool
+
+
+class TargetAttentionPool(nn.Module):
+    """forward(query [B, D], seq [B, L, D+1]) -> [B, D]; scale 1/sqrt(D)
+    unless given."""
+
+    def __init__(self, scale: Optional[float] = None):
+        super().__init__()
+        self.scale = scale
+
+    def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
+        return seq_attn_pool(query, seq, self.scale)
+
+
+class SeqCTR(nn.Module):
+    """``dims[i]`` is the dim of embedding tensor i (in ``embedding_tensors``
+    order); ``seq_query`` maps the index of each sequence tensor to the index
+    of the sum slot that is its query.  Every sequence is pooled to ``(B,
+    dim)``; the pooled vectors, all sum slots (queries included) and the dense
+    features are concatenated and run through an MLP to one logit.
+
+    ``fused=True`` runs the MLP on the MFMA kernels (ops/dense.py FusedMLP,
+    hidden widths % 32 == 0) in bf16, with the input zero-padded to a
+    multiple of 32 as in DCNv2."""
+
+    def __init__(
+        self,
+        dims: Sequence[int],
+        seq_query: Dict[int, int],
+        num_dense: int = 13,
+        hidden: Sequence[int] = (256, 128),
+        fused: bool = False,
+    ):
+        super().__init__()
+        for s, qi in seq_query.items():
+            assert qi not in seq_query, f"query {qi} of sequence {s} is a sequence"
+            assert dims[s] == dims[qi], \
+                f"sequence {s} (dim {dims[s]}) and its query {qi} (dim {dims[qi]})"
+        self.seq_query = {int(s): int(qi) for s, qi in seq_query.items()}
+        self.num_dense = num_dense
+        self.pool = TargetAttentionPool()
+        in_dim = num_dense + sum(dims)
+        self.fused = fused
+        self.pad = (-in_dim) % 32 if fused else 0
+        in_dim += self.pad
+        sizes = [in_dim] + list(hidden) + [1]
+        if fused:
+            from persia_amd.ops.dense import FusedMLP
+
+            self.mlp = FusedMLP(sizes)
+        else:
+            layers: List[nn.Module] = []
+            for i in range(len(sizes) - 1):
+                layers.append(nn.Linear(sizes[i], sizes[i + 1]))
+                if i < len(sizes) - 2:
+                    layers.append(nn.ReLU())
+            self.mlp = nn.Sequential(*layers)
+
+    def forward(self, non_id_tensors, embedding_tensors) -> torch.Tensor:
+        dt = torch.bfloat16 if self.fused else torch.float32
+        feats = []
+        if self.num_dense:
+            dense = (non_id_tensors if torch.is_tensor(non_id_tensors)
+                     else non_id_tensors[0])
+            feats.append(dense.to(dt))
+        for i, e in enumerate(embedding_tensors):
+            qi = self.seq_query.get(i)
+            if qi is not None:
+                e = self.pool(embedding_tensors[qi], e)
+            feats.append(e.to(dt))
+        x = torch.cat(feats, dim=1)
+        if self.pad:
+            x = torch.nn.functional.pad(x, (0, self.pad))
+        return self.mlp(x).squeeze(1).float()

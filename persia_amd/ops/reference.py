@@ -199,3 +199,40 @@ def ftrl_update(
     emb.copy_((z.clamp(-l1, l1) - z) / q)
     if weight_bound > 0:
         emb.clamp_(-weight_bound, weight_bound)
+
+
+# ------------------------------------------------- target-attention pooling
+
+
+def seq_attn_pool_reference(
+    q: torch.Tensor,  # [B, D]
+    seq: torch.Tensor,  # [B, L, D+1] — channel D is the 0/1 mask
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """DIN-style target attention over a raw slot's tensor, plain torch (not
+    in the reference; csrc/seqattn.hip is the HIP twin):
+
+        s_l = scale * <q, k_l>,  p = softmax of s over the valid l,
+        out = sum_{valid l} p_l * k_l                     -> [B, D], q's dtype
+
+    with k_l = seq[:, l, :D] and valid_l = (seq[:, l, D] != 0); scale defaults
+    to 1/sqrt(D).  The mask selects and never multiplies: an invalid row is
+    replaced by zeros before any arithmetic, so an Inf or NaN there reaches
+    neither the output nor a gradient.  A sample without a valid cell gives
+    zeros.  Computes in f32 (f64 for f64 inputs); differentiable in q and seq
+    (the mask channel's gradient is zero)."""
+    D = q.shape[-1]
+    if scale is None:
+        scale = float(D) ** -0.5
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    valid = seq[..., D] != 0
+    k = seq[..., :D].to(ct)
+    k = torch.where(valid.unsqueeze(-1), k, torch.zeros((), dtype=ct, device=k.device))
+    s = scale * (k * q.to(ct).unsqueeze(1)).sum(-1)
+    s = s.masked_fill(~valid, float("-inf"))
+    m = s.max(dim=1, keepdim=True).values
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    e = torch.exp(s - m)  # 0 at an invalid cell
+    den = e.sum(dim=1, keepdim=True)
+    p = e / torch.where(den > 0, den, torch.ones_like(den))
+    return (p.unsqueeze(-1) * k).sum(dim=1).to(q.dtype)
