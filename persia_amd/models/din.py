@@ -5,12 +5,16 @@ A raw (sequence) slot arrives as ``(B, sample_fixed_size, dim+1)`` with the
 dim)`` with the candidate item's embedding (a sum slot of the same dim) as
 the query — scaled dot-product scores, softmax over the valid cells, weighted
 sum of the rows (ops/seqattn.py: one HIP kernel per direction on the GPU, the
-torch reference on CPU)."""
+torch reference on CPU).  ``ActivationUnitPool`` is DIN's own attention: a
+small MLP over ``[q, k, q-k, q*k]`` scores each row and the scores weight a
+plain sum, without a softmax (ops/actunit.py, MFMA kernels on the GPU)."""
+import math
 from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
+from persia_amd.ops.actunit import act_unit_pool
 from persia_amd.ops.seqattn import seq_attn_pool
 
 
@@ -26,6 +30,24 @@ class TargetAttentionPool(nn.Module):
         return seq_attn_pool(query, seq, self.scale)
 
 
+class ActivationUnitPool(nn.Module):
+    """DIN's local activation unit: forward(query [B, D], seq [B, L, D+1]) ->
+    [B, D] = sum over the valid rows k_l of (w2 . sigmoid(W1 [q; k_l; q-k_l;
+    q*k_l] + b1) + b2) * k_l.  The parameters are f32 masters."""
+
+    def __init__(self, dim: int, hidden: int = 32):
+        super().__init__()
+        self.dim, self.hidden = dim, hidden
+        bound1, bound2 = 1.0 / math.sqrt(4 * dim), 1.0 / math.sqrt(hidden)
+        self.W1 = nn.Parameter(torch.empty(hidden, 4 * dim).uniform_(-bound1, bound1))
+        self.b1 = nn.Parameter(torch.empty(hidden).uniform_(-bound1, bound1))
+        self.w2 = nn.Parameter(torch.empty(hidden).uniform_(-bound2, bound2))
+        self.b2 = nn.Parameter(torch.empty(()).uniform_(-bound2, bound2))
+
+    def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
+        return act_unit_pool(query, seq, self.W1, self.b1, self.w2, self.b2)
+
+
 class SeqCTR(nn.Module):
     """``dims[i]`` is the dim of embedding tensor i (in ``embedding_tensors``
     order); ``seq_query`` maps the index of each sequence tensor to the index
@@ -35,7 +57,11 @@ class SeqCTR(nn.Module):
 
     ``fused=True`` runs the MLP on the MFMA kernels (ops/dense.py FusedMLP,
     hidden widths % 32 == 0) in bf16, with the input zero-padded to a
-    multiple of 32 as in DCNv2."""
+    multiple of 32 as in DCNv2.
+
+    ``attention="dot"`` pools with ``TargetAttentionPool``; ``"mlp"`` gives
+    every sequence an ``ActivationUnitPool`` of its own with ``att_hidden``
+    hidden units (``self.act_pools[str(index)]``)."""
 
     def __init__(
         self,
@@ -44,6 +70,8 @@ class SeqCTR(nn.Module):
         num_dense: int = 13,
         hidden: Sequence[int] = (256, 128),
         fused: bool = False,
+        attention: str = "dot",
+        att_hidden: int = 32,
     ):
         super().__init__()
         for s, qi in seq_query.items():
@@ -52,7 +80,14 @@ class SeqCTR(nn.Module):
                 f"sequence {s} (dim {dims[s]}) and its query {qi} (dim {dims[qi]})"
         self.seq_query = {int(s): int(qi) for s, qi in seq_query.items()}
         self.num_dense = num_dense
-        self.pool = TargetAttentionPool()
+        assert attention in ("dot", "mlp"), attention
+        self.attention = attention
+        if attention == "dot":
+            self.pool = TargetAttentionPool()
+        else:
+            self.act_pools = nn.ModuleDict({
+                str(s): ActivationUnitPool(dims[s], att_hidden)
+                for s in sorted(self.seq_query)})
         in_dim = num_dense + sum(dims)
         self.fused = fused
         self.pad = (-in_dim) % 32 if fused else 0
@@ -80,7 +115,9 @@ class SeqCTR(nn.Module):
         for i, e in enumerate(embedding_tensors):
             qi = self.seq_query.get(i)
             if qi is not None:
-                e = self.pool(embedding_tensors[qi], e)
+                pool = (self.pool if self.attention == "dot"
+                        else self.act_pools[str(i)])
+                e = pool(embedding_tensors[qi], e)
             feats.append(e.to(dt))
         x = torch.cat(feats, dim=1)
         if self.pad:

@@ -236,3 +236,66 @@ def seq_attn_pool_reference(
     den = e.sum(dim=1, keepdim=True)
     p = e / torch.where(den > 0, den, torch.ones_like(den))
     return (p.unsqueeze(-1) * k).sum(dim=1).to(q.dtype)
+
+
+# ------------------------------------------- activation-unit (MLP) pooling
+
+
+def _round_f16_st(x: torch.Tensor) -> torch.Tensor:
+    """x with the value of its f16 rounding (through f32, as the kernel
+    rounds) and the gradient of the identity."""
+    return x + (x.float().half().to(x.dtype) - x).detach()
+
+
+def act_unit_prepared_reference(
+    q: torch.Tensor,  # [B, D]
+    seq: torch.Tensor,  # [B, L, D+1] — channel D is the 0/1 mask
+    u: torch.Tensor,  # [B, H] = (Wq+Wd) q + b1
+    Wb: torch.Tensor,  # [H, D] = Wk-Wd
+    Wp: torch.Tensor,  # [H, D]
+    w2: torch.Tensor,  # [H]
+    b2: torch.Tensor,  # []
+) -> torch.Tensor:
+    """The part of ``act_unit_pool_reference`` the HIP kernels compute
+    (csrc/actunit.hip takes the same operands), differentiable in all of
+    them.  ``Wb``, ``Wp`` and ``M_b = Wb + Wp * q_b`` are rounded to f16,
+    straight-through: the rounding is part of the definition."""
+    D = q.shape[-1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    valid = seq[..., D] != 0
+    k = seq[..., :D].to(ct)
+    k = torch.where(valid.unsqueeze(-1), k, torch.zeros((), dtype=ct, device=k.device))
+    Wb, Wp = _round_f16_st(Wb.to(ct)), _round_f16_st(Wp.to(ct))
+    M = _round_f16_st(Wb.unsqueeze(0) + Wp.unsqueeze(0) * q.to(ct).unsqueeze(1))
+    h = u.to(ct).unsqueeze(1) + k @ M.transpose(1, 2)  # [B, L, H]
+    w = torch.sigmoid(h) @ w2.to(ct) + b2.to(ct)
+    w = torch.where(valid, w, torch.zeros((), dtype=ct, device=k.device))
+    return (w.unsqueeze(-1) * k).sum(dim=1).to(q.dtype)
+
+
+def act_unit_pool_reference(
+    q: torch.Tensor,  # [B, D]
+    seq: torch.Tensor,  # [B, L, D+1] — channel D is the 0/1 mask
+    W1: torch.Tensor,  # [H, 4D], column blocks Wq | Wk | Wd | Wp
+    b1: torch.Tensor,  # [H]
+    w2: torch.Tensor,  # [H]
+    b2: torch.Tensor,  # []
+) -> torch.Tensor:
+    """DIN's local activation unit over a raw slot's tensor, plain torch (not
+    in the reference; csrc/actunit.hip is the HIP twin):
+
+        h_l = W1 [q; k_l; q-k_l; q*k_l] + b1
+            = u + M k_l,  u = (Wq+Wd) q + b1,  M = (Wk-Wd) + Wp * q
+        w_l = <w2, sigmoid(h_l)> + b2
+        out = sum_{valid l} w_l * k_l                     -> [B, D], q's dtype
+
+    No softmax: the score is the weight.  The mask selects as in
+    ``seq_attn_pool_reference`` (invalid rows are zeros before any
+    arithmetic; a sample without a valid cell gives zeros).  Computes in f32
+    (f64 for f64 inputs); the f16 roundings of ``M`` and of its two weight
+    blocks are straight-through.  Differentiable in everything."""
+    D = q.shape[-1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    Wq, Wk, Wd, Wp = (W1[:, i * D:(i + 1) * D].to(ct) for i in range(4))
+    u = torch.addmm(b1.to(ct), q.to(ct), (Wq + Wd).t())
+    return act_unit_prepared_reference(q, seq, u, Wk - Wd, Wp, w2, b2)
