@@ -7,7 +7,10 @@ the query — scaled dot-product scores, softmax over the valid cells, weighted
 sum of the rows (ops/seqattn.py: one HIP kernel per direction on the GPU, the
 torch reference on CPU).  ``ActivationUnitPool`` is DIN's own attention: a
 small MLP over ``[q, k, q-k, q*k]`` scores each row and the scores weight a
-plain sum, without a softmax (ops/actunit.py, MFMA kernels on the GPU)."""
+plain sum, without a softmax (ops/actunit.py, MFMA kernels on the GPU).
+``InterestGRUPool`` models the order of the sequence: a GRU over the rows,
+or DIEN's attention-gated AUGRU, whose last state is the pooled vector
+(ops/seqgru.py, a persistent MFMA kernel per direction on the GPU)."""
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -16,6 +19,7 @@ import torch.nn as nn
 
 from persia_amd.ops.actunit import act_unit_pool
 from persia_amd.ops.seqattn import seq_attn_pool
+from persia_amd.ops.seqgru import seq_gru
 
 
 class TargetAttentionPool(nn.Module):
@@ -48,6 +52,46 @@ class ActivationUnitPool(nn.Module):
         return act_unit_pool(query, seq, self.W1, self.b1, self.w2, self.b2)
 
 
+class InterestGRUPool(nn.Module):
+    """forward(query [B, D], seq [B, L, D+1]) -> [B, hidden]: the state of a
+    GRU over the rows after the last valid one.  Parameters are f32 masters in
+    ``torch.nn.GRU``'s layout and init (``weight_ih_l0`` ...), so a trained
+    ``nn.GRU``'s state dict loads unchanged.  With ``attention=True`` the
+    update gate of every row is scaled by its attention weight -- the softmax
+    over the valid rows of <q, k_l>/sqrt(D), zero for a sample without a valid
+    row -- which is DIEN's AUGRU; the query is ignored otherwise."""
+
+    def __init__(self, dim: int, hidden: Optional[int] = None,
+                 attention: bool = False):
+        super().__init__()
+        self.dim, self.hidden = dim, dim if hidden is None else hidden
+        self.attention = attention
+        bound = 1.0 / math.sqrt(self.hidden)
+        for name, shape in (("weight_ih_l0", (3 * self.hidden, dim)),
+                            ("weight_hh_l0", (3 * self.hidden, self.hidden)),
+                            ("bias_ih_l0", (3 * self.hidden,)),
+                            ("bias_hh_l0", (3 * self.hidden,))):
+            setattr(self, name,
+                    nn.Parameter(torch.empty(*shape).uniform_(-bound, bound)))
+
+    def attention_weights(self, query: torch.Tensor, seq: torch.Tensor):
+        """-> f32 [B, L]: softmax of <q, k_l>/sqrt(D) over the valid rows."""
+        valid = seq[..., self.dim] != 0
+        k = torch.where(valid.unsqueeze(-1), seq[..., :self.dim].float(),
+                        torch.zeros((), device=seq.device))
+        s = (k * query.float().unsqueeze(1)).sum(-1) * self.dim ** -0.5
+        s = s.masked_fill(~valid, float("-inf"))
+        m = s.max(dim=1, keepdim=True).values
+        e = torch.exp(s - torch.where(torch.isfinite(m), m, torch.zeros_like(m)))
+        den = e.sum(dim=1, keepdim=True)
+        return e / torch.where(den > 0, den, torch.ones_like(den))
+
+    def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
+        att = self.attention_weights(query, seq) if self.attention else None
+        return seq_gru(seq, self.weight_ih_l0, self.weight_hh_l0,
+                       self.bias_ih_l0, self.bias_hh_l0, att)[1]
+
+
 class SeqCTR(nn.Module):
     """``dims[i]`` is the dim of embedding tensor i (in ``embedding_tensors``
     order); ``seq_query`` maps the index of each sequence tensor to the index
@@ -61,7 +105,10 @@ class SeqCTR(nn.Module):
 
     ``attention="dot"`` pools with ``TargetAttentionPool``; ``"mlp"`` gives
     every sequence an ``ActivationUnitPool`` of its own with ``att_hidden``
-    hidden units (``self.act_pools[str(index)]``)."""
+    hidden units (``self.act_pools[str(index)]``); ``"gru"`` and ``"augru"``
+    give it an ``InterestGRUPool`` (``self.gru_pools[str(index)]``) whose
+    hidden size is the slot's dim, so the MLP's input width stays what it
+    is."""
 
     def __init__(
         self,
@@ -80,10 +127,14 @@ class SeqCTR(nn.Module):
                 f"sequence {s} (dim {dims[s]}) and its query {qi} (dim {dims[qi]})"
         self.seq_query = {int(s): int(qi) for s, qi in seq_query.items()}
         self.num_dense = num_dense
-        assert attention in ("dot", "mlp"), attention
+        assert attention in ("dot", "mlp", "gru", "augru"), attention
         self.attention = attention
         if attention == "dot":
             self.pool = TargetAttentionPool()
+        elif attention in ("gru", "augru"):
+            self.gru_pools = nn.ModuleDict({
+                str(s): InterestGRUPool(dims[s], attention=attention == "augru")
+                for s in sorted(self.seq_query)})
         else:
             self.act_pools = nn.ModuleDict({
                 str(s): ActivationUnitPool(dims[s], att_hidden)
@@ -116,7 +167,8 @@ class SeqCTR(nn.Module):
             qi = self.seq_query.get(i)
             if qi is not None:
                 pool = (self.pool if self.attention == "dot"
-                        else self.act_pools[str(i)])
+                        else self.act_pools[str(i)] if self.attention == "mlp"
+                        else self.gru_pools[str(i)])
                 e = pool(embedding_tensors[qi], e)
             feats.append(e.to(dt))
         x = torch.cat(feats, dim=1)

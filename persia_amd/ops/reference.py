@@ -299,3 +299,57 @@ def act_unit_pool_reference(
     Wq, Wk, Wd, Wp = (W1[:, i * D:(i + 1) * D].to(ct) for i in range(4))
     u = torch.addmm(b1.to(ct), q.to(ct), (Wq + Wd).t())
     return act_unit_prepared_reference(q, seq, u, Wk - Wd, Wp, w2, b2)
+
+
+# ------------------------------------------------- GRU / AUGRU over a raw slot
+
+
+def seq_gru_reference(
+    seq: torch.Tensor,  # [B, L, D+1] — channel D is the 0/1 mask
+    Wx: torch.Tensor,  # [3H, D], gates (r, z, n) as nn.GRU's weight_ih_l0
+    Wh: torch.Tensor,  # [3H, H], as weight_hh_l0
+    bx: torch.Tensor,  # [3H]
+    bh: torch.Tensor,  # [3H]
+    att: Optional[torch.Tensor] = None,  # [B, L]
+    operand_dtype: Optional[torch.dtype] = None,
+):
+    """GRU (``att`` None: exactly ``torch.nn.GRU`` on the valid rows) or DIEN's
+    AUGRU over a raw slot's tensor, plain torch (not in the reference;
+    csrc/seqgru.hip is the HIP twin).  With h_{-1} = 0 and x_t = seq[:, t, :D]:
+
+        valid t:   r = sigmoid(Wx_r x + bx_r + Wh_r h + bh_r),  z alike,
+                   n = tanh(Wx_n x + bx_n + r * (Wh_n h + bh_n)),
+                   h_t = h + a_t (1 - z) (n - h)
+        invalid t: h_t = h_{t-1}
+
+    -> (states [B, L, H], last [B, H] = states[:, L-1]) in seq's dtype.  The
+    mask selects: invalid rows, and the ``att`` of invalid rows, are replaced
+    by zeros before any arithmetic.  Computes in f32 (f64 for f64 inputs); the
+    f16 rounding of ``Wx`` and ``Wh`` is part of the definition and
+    straight-through, the state is a continuous recurrence.
+    ``operand_dtype=torch.float16`` additionally rounds, straight-through, the
+    ``h`` that multiplies ``Wh`` and the ``h`` of the update -- the kernels'
+    approximation, emulated only to size the tests' bounds."""
+    D, H = seq.shape[-1] - 1, Wh.shape[1]
+    ct = torch.float64 if seq.dtype == torch.float64 else torch.float32
+    zero = torch.zeros((), dtype=ct, device=seq.device)
+    valid = seq[..., D] != 0
+    x = torch.where(valid.unsqueeze(-1), seq[..., :D].to(ct), zero)
+    a = None if att is None else torch.where(valid, att.to(ct), zero)
+    Wx, Wh = _round_f16_st(Wx.to(ct)), _round_f16_st(Wh.to(ct))
+    gx = x @ Wx.t() + bx.to(ct)  # [B, L, 3H]
+    h = torch.zeros(seq.shape[0], H, dtype=ct, device=seq.device)
+    states = []
+    for t in range(seq.shape[1]):
+        hq = _round_f16_st(h) if operand_dtype == torch.float16 else h
+        gh = hq @ Wh.t() + bh.to(ct)
+        r = torch.sigmoid(gx[:, t, :H] + gh[:, :H])
+        z = torch.sigmoid(gx[:, t, H:2 * H] + gh[:, H:2 * H])
+        n = torch.tanh(gx[:, t, 2 * H:] + r * gh[:, 2 * H:])
+        step = (1 - z) * (n - hq)
+        if a is not None:
+            step = a[:, t].unsqueeze(-1) * step
+        h = torch.where(valid[:, t].unsqueeze(-1), hq + step, h)
+        states.append(h)
+    states = torch.stack(states, dim=1).to(seq.dtype)
+    return states, states[:, -1]

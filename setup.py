@@ -21,6 +21,7 @@ ext = CUDAExtension(
         "persia_amd/csrc/interact.hip",
         "persia_amd/csrc/seqattn.hip",
         "persia_amd/csrc/actunit.hip",
+        "persia_amd/csrc/seqgru.hip",
         "persia_amd/csrc/checkpoint.hip",
         "persia_amd/csrc/engine.cpp",
     ],
