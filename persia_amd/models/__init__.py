@@ -7,8 +7,9 @@ plug directly into ``ctx.forward``.
 from persia_amd.models.ctr import CTRModel
 from persia_amd.models.dlrm import DLRM
 from persia_amd.models.dcn import DCNv2
-from persia_amd.models.din import (ActivationUnitPool, InterestGRUPool, SeqCTR,
+from persia_amd.models.din import (ActivationUnitPool, InterestGRUPool,
+                                   SelfAttentionPool, SeqCTR,
                                    TargetAttentionPool)
 
 __all__ = ["CTRModel", "DLRM", "DCNv2", "SeqCTR", "TargetAttentionPool",
-           "ActivationUnitPool", "InterestGRUPool"]
+           "ActivationUnitPool", "InterestGRUPool", "SelfAttentionPool"]

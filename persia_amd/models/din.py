@@ -10,7 +10,10 @@ small MLP over ``[q, k, q-k, q*k]`` scores each row and the scores weight a
 plain sum, without a softmax (ops/actunit.py, MFMA kernels on the GPU).
 ``InterestGRUPool`` models the order of the sequence: a GRU over the rows,
 or DIEN's attention-gated AUGRU, whose last state is the pooled vector
-(ops/seqgru.py, a persistent MFMA kernel per direction on the GPU)."""
+(ops/seqgru.py, a persistent MFMA kernel per direction on the GPU).
+``SelfAttentionPool`` first lets the rows attend to each other (multi-head
+self-attention, ops/seqsa.py, one MFMA kernel per direction) and then pools
+the result with the target attention above."""
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -20,6 +23,7 @@ import torch.nn as nn
 from persia_amd.ops.actunit import act_unit_pool
 from persia_amd.ops.seqattn import seq_attn_pool
 from persia_amd.ops.seqgru import seq_gru
+from persia_amd.ops.seqsa import seq_self_attn
 
 
 class TargetAttentionPool(nn.Module):
@@ -92,6 +96,42 @@ class InterestGRUPool(nn.Module):
                        self.bias_ih_l0, self.bias_hh_l0, att)[1]
 
 
+class SelfAttentionLayer(nn.Module):
+    """forward(seq [B, L, D+1], Wqkv, bqkv) -> [B, L, D+1]: ``seq_self_attn``
+    with a residual; holds no parameters of its own."""
+
+    def __init__(self, heads: int, causal: bool = False):
+        super().__init__()
+        self.heads, self.causal = heads, causal
+
+    def forward(self, seq, Wqkv, bqkv) -> torch.Tensor:
+        return seq_self_attn(seq, Wqkv, bqkv, self.heads, self.causal,
+                             residual=True)
+
+
+class SelfAttentionPool(nn.Module):
+    """forward(query [B, D], seq [B, L, D+1]) -> [B, D]: multi-head
+    self-attention among the valid rows with a residual (``causal``: a row
+    sees the rows not after it, as in SASRec; otherwise all of them, as in
+    the Behavior Sequence Transformer), then target attention of the
+    candidate over the result.  ``in_proj_weight`` / ``in_proj_bias`` are f32
+    masters in ``torch.nn.MultiheadAttention``'s layout and init, so a trained
+    module's tensors load unchanged."""
+
+    def __init__(self, dim: int, heads: int = 2, causal: bool = False):
+        super().__init__()
+        assert dim % heads == 0, f"{heads} heads do not divide dim {dim}"
+        self.dim, self.heads, self.causal = dim, heads, causal
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        self.layer = SelfAttentionLayer(heads, causal)
+
+    def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
+        return seq_attn_pool(
+            query, self.layer(seq, self.in_proj_weight, self.in_proj_bias))
+
+
 class SeqCTR(nn.Module):
     """``dims[i]`` is the dim of embedding tensor i (in ``embedding_tensors``
     order); ``seq_query`` maps the index of each sequence tensor to the index
@@ -108,7 +148,8 @@ class SeqCTR(nn.Module):
     hidden units (``self.act_pools[str(index)]``); ``"gru"`` and ``"augru"``
     give it an ``InterestGRUPool`` (``self.gru_pools[str(index)]``) whose
     hidden size is the slot's dim, so the MLP's input width stays what it
-    is."""
+    is; ``"self"`` gives it a ``SelfAttentionPool`` with ``heads`` heads
+    (``self.sa_pools[str(index)]``)."""
 
     def __init__(
         self,
@@ -119,6 +160,7 @@ class SeqCTR(nn.Module):
         fused: bool = False,
         attention: str = "dot",
         att_hidden: int = 32,
+        heads: int = 2,
     ):
         super().__init__()
         for s, qi in seq_query.items():
@@ -127,13 +169,17 @@ class SeqCTR(nn.Module):
                 f"sequence {s} (dim {dims[s]}) and its query {qi} (dim {dims[qi]})"
         self.seq_query = {int(s): int(qi) for s, qi in seq_query.items()}
         self.num_dense = num_dense
-        assert attention in ("dot", "mlp", "gru", "augru"), attention
+        assert attention in ("dot", "mlp", "gru", "augru", "self"), attention
         self.attention = attention
         if attention == "dot":
             self.pool = TargetAttentionPool()
         elif attention in ("gru", "augru"):
             self.gru_pools = nn.ModuleDict({
                 str(s): InterestGRUPool(dims[s], attention=attention == "augru")
+                for s in sorted(self.seq_query)})
+        elif attention == "self":
+            self.sa_pools = nn.ModuleDict({
+                str(s): SelfAttentionPool(dims[s], heads)
                 for s in sorted(self.seq_query)})
         else:
             self.act_pools = nn.ModuleDict({
@@ -168,6 +214,7 @@ class SeqCTR(nn.Module):
             if qi is not None:
                 pool = (self.pool if self.attention == "dot"
                         else self.act_pools[str(i)] if self.attention == "mlp"
+                        else self.sa_pools[str(i)] if self.attention == "self"
                         else self.gru_pools[str(i)])
                 e = pool(embedding_tensors[qi], e)
             feats.append(e.to(dt))

@@ -353,3 +353,63 @@ def seq_gru_reference(
         states.append(h)
     states = torch.stack(states, dim=1).to(seq.dtype)
     return states, states[:, -1]
+
+
+# ------------------------------------------- self-attention among a raw slot
+
+
+def seq_self_attn_reference(
+    seq: torch.Tensor,  # [B, L, D+1] — channel D is the 0/1 mask
+    Wqkv: torch.Tensor,  # [3D, D], rows q | k | v as MultiheadAttention's in_proj_weight
+    bqkv: torch.Tensor,  # [3D]
+    heads: int,
+    causal: bool = False,
+    residual: bool = False,
+    operand_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    """Multi-head self-attention among the rows of a raw slot's tensor, plain
+    torch (not in the reference; csrc/seqsa.hip is the HIP twin).  With x_i =
+    seq[:, i, :D], dh = D / heads and W16 = f16(Wqkv):
+
+        valid i:   [q_i | k_i | v_i] = W16 x_i + bqkv
+                   s_ij = dh^-1/2 <q_i^h, k_j^h> per head h;  j is allowed for
+                   i iff row j is valid and (not causal or j <= i)
+                   p_i. = softmax over the allowed j;  o_i^h = sum_j p_ij v_j^h
+                   out_i = o_i (+ x_i if residual)
+        invalid i: out_i = 0
+
+    -> [B, L, D+1] in seq's dtype with out[..., D] = seq[..., D], a raw-slot
+    tensor again.  The mask selects: invalid rows are replaced by zeros before
+    any arithmetic and their keys are never allowed, so an Inf or NaN there
+    reaches neither an output nor a gradient; a valid row always allows
+    itself.  Computes in f32 (f64 for f64 inputs); the f16 rounding of
+    ``Wqkv`` is part of the definition and straight-through.
+    ``operand_dtype=torch.float16`` additionally rounds, straight-through, q,
+    k, v after the projection and p before ``PV`` -- the kernels' MFMA
+    operands, emulated only to size the tests' bounds."""
+    B, L, D = seq.shape[0], seq.shape[1], seq.shape[2] - 1
+    dh = D // heads
+    ct = torch.float64 if seq.dtype == torch.float64 else torch.float32
+    zero = torch.zeros((), dtype=ct, device=seq.device)
+    valid = seq[..., D] != 0
+    x = torch.where(valid.unsqueeze(-1), seq[..., :D].to(ct), zero)
+    rnd = _round_f16_st if operand_dtype == torch.float16 else (lambda t: t)
+    qkv = rnd(x @ _round_f16_st(Wqkv.to(ct)).t() + bqkv.to(ct))
+    q, k, v = (t.reshape(B, L, heads, dh).transpose(1, 2)
+               for t in qkv.split(D, dim=-1))  # [B, heads, L, dh]
+    allowed = valid.unsqueeze(1).expand(B, L, L)  # [B, i, j]
+    if causal:
+        allowed = allowed & torch.ones(L, L, dtype=torch.bool,
+                                       device=seq.device).tril()
+    allowed = allowed.unsqueeze(1)
+    s = (q @ k.transpose(2, 3)) * float(dh) ** -0.5
+    s = s.masked_fill(~allowed, float("-inf"))
+    m = s.max(dim=-1, keepdim=True).values
+    e = torch.exp(s - torch.where(torch.isfinite(m), m, torch.zeros_like(m)))
+    den = e.sum(dim=-1, keepdim=True)
+    p = rnd(e / torch.where(den > 0, den, torch.ones_like(den)))
+    o = (p @ v).transpose(1, 2).reshape(B, L, D)
+    if residual:
+        o = o + x
+    o = torch.where(valid.unsqueeze(-1), o, zero)
+    return torch.cat([o.to(seq.dtype), seq[..., D:].detach()], dim=-1)

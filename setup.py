@@ -22,6 +22,7 @@ ext = CUDAExtension(
         "persia_amd/csrc/seqattn.hip",
         "persia_amd/csrc/actunit.hip",
         "persia_amd/csrc/seqgru.hip",
+        "persia_amd/csrc/seqsa.hip",
         "persia_amd/csrc/checkpoint.hip",
         "persia_amd/csrc/engine.cpp",
     ],
