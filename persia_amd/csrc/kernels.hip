@@ -2511,6 +2511,7 @@ void init_seqattn(pybind11::module_& m);   // csrc/seqattn.hip
 void init_actunit(pybind11::module_& m);   // csrc/actunit.hip
 void init_seqgru(pybind11::module_& m);    // csrc/seqgru.hip
 void init_seqsa(pybind11::module_& m);     // csrc/seqsa.hip
+void init_seqffn(pybind11::module_& m);    // csrc/seqffn.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "persia_amd HIP kernels (gfx950)";
@@ -2521,6 +2522,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_actunit(m);
   init_seqgru(m);
   init_seqsa(m);
+  init_seqffn(m);
   init_checkpoint(m);
   m.def("store_lookup", &store_lookup, "hash-table lookup/insert + gather");
   m.def("store_probe", &store_probe, "probe-only (spill-tier miss detection)");

@@ -8,8 +8,8 @@ from persia_amd.models.ctr import CTRModel
 from persia_amd.models.dlrm import DLRM
 from persia_amd.models.dcn import DCNv2
 from persia_amd.models.din import (ActivationUnitPool, InterestGRUPool,
-                                   SelfAttentionPool, SeqCTR,
+                                   SelfAttentionPool, SeqCTR, SeqEncoderLayer,
                                    TargetAttentionPool)
 
 __all__ = ["CTRModel", "DLRM", "DCNv2", "SeqCTR", "TargetAttentionPool",
-           "ActivationUnitPool", "InterestGRUPool", "SelfAttentionPool"]
+           "ActivationUnitPool", "InterestGRUPool", "SelfAttentionPool", "SeqEncoderLayer"]

@@ -13,7 +13,11 @@ or DIEN's attention-gated AUGRU, whose last state is the pooled vector
 (ops/seqgru.py, a persistent MFMA kernel per direction on the GPU).
 ``SelfAttentionPool`` first lets the rows attend to each other (multi-head
 self-attention, ops/seqsa.py, one MFMA kernel per direction) and then pools
-the result with the target attention above."""
+the result with the target attention above.  ``SeqEncoderLayer`` is the
+whole post-norm transformer block -- that self-attention followed by the
+out-projection, add & LayerNorm and the feed-forward (ops/seqffn.py, one more
+MFMA kernel per direction) -- under ``nn.TransformerEncoderLayer``'s parameter
+names."""
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -23,6 +27,7 @@ import torch.nn as nn
 from persia_amd.ops.actunit import act_unit_pool
 from persia_amd.ops.seqattn import seq_attn_pool
 from persia_amd.ops.seqgru import seq_gru
+from persia_amd.ops.seqffn import seq_ffn
 from persia_amd.ops.seqsa import seq_self_attn
 
 
@@ -109,6 +114,45 @@ class SelfAttentionLayer(nn.Module):
                              residual=True)
 
 
+class _InProj(nn.Module):
+    """The parameters of ``nn.MultiheadAttention``, under its names."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        self.out_proj = nn.Linear(dim, dim)
+        nn.init.zeros_(self.out_proj.bias)
+
+
+class SeqEncoderLayer(nn.Module):
+    """forward(seq [B, L, D+1]) -> [B, L, D+1]: a post-norm transformer
+    encoder layer (ReLU, no dropout) among the valid rows of a raw slot --
+    BST's layer, SASRec's with ``causal`` -- as ``seq_self_attn`` followed by
+    ``seq_ffn``.  The parameters are f32 masters with the names, layouts and
+    init of ``nn.TransformerEncoderLayer(dim, heads, ffn, dropout=0.0)``, so
+    ``load_state_dict(nn_layer.state_dict())`` works."""
+
+    def __init__(self, dim: int, heads: int, ffn: int, causal: bool = False,
+                 eps: float = 1e-5):
+        super().__init__()
+        assert dim % heads == 0, f"{heads} heads do not divide dim {dim}"
+        self.dim, self.heads, self.ffn, self.causal = dim, heads, ffn, causal
+        self.self_attn = _InProj(dim)
+        self.linear1, self.linear2 = nn.Linear(dim, ffn), nn.Linear(ffn, dim)
+        self.norm1, self.norm2 = nn.LayerNorm(dim, eps=eps), nn.LayerNorm(dim, eps=eps)
+
+    def forward(self, seq: torch.Tensor) -> torch.Tensor:
+        sa, n1, n2 = self.self_attn, self.norm1, self.norm2
+        a = seq_self_attn(seq, sa.in_proj_weight, sa.in_proj_bias, self.heads,
+                          self.causal, residual=False)
+        return seq_ffn(seq, a, sa.out_proj.weight, sa.out_proj.bias, n1.weight,
+                       n1.bias, self.linear1.weight, self.linear1.bias,
+                       self.linear2.weight, self.linear2.bias, n2.weight,
+                       n2.bias, n1.eps)
+
+
 class SelfAttentionPool(nn.Module):
     """forward(query [B, D], seq [B, L, D+1]) -> [B, D]: multi-head
     self-attention among the valid rows with a residual (``causal``: a row
@@ -116,18 +160,26 @@ class SelfAttentionPool(nn.Module):
     the Behavior Sequence Transformer), then target attention of the
     candidate over the result.  ``in_proj_weight`` / ``in_proj_bias`` are f32
     masters in ``torch.nn.MultiheadAttention``'s layout and init, so a trained
-    module's tensors load unchanged."""
+    module's tensors load unchanged.  With ``ffn`` given the rows run
+    through a whole ``SeqEncoderLayer`` (``self.encoder``) with that hidden
+    width instead, and its output is pooled."""
 
-    def __init__(self, dim: int, heads: int = 2, causal: bool = False):
+    def __init__(self, dim: int, heads: int = 2, causal: bool = False,
+                 ffn: Optional[int] = None):
         super().__init__()
         assert dim % heads == 0, f"{heads} heads do not divide dim {dim}"
         self.dim, self.heads, self.causal = dim, heads, causal
+        if ffn is not None:
+            self.encoder = SeqEncoderLayer(dim, heads, ffn, causal)
+            return
         self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
         self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
         nn.init.xavier_uniform_(self.in_proj_weight)
         self.layer = SelfAttentionLayer(heads, causal)
 
     def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
+        if hasattr(self, "encoder"):
+            return seq_attn_pool(query, self.encoder(seq))
         return seq_attn_pool(
             query, self.layer(seq, self.in_proj_weight, self.in_proj_bias))
 
@@ -149,7 +201,8 @@ class SeqCTR(nn.Module):
     give it an ``InterestGRUPool`` (``self.gru_pools[str(index)]``) whose
     hidden size is the slot's dim, so the MLP's input width stays what it
     is; ``"self"`` gives it a ``SelfAttentionPool`` with ``heads`` heads
-    (``self.sa_pools[str(index)]``)."""
+    (``self.sa_pools[str(index)]``); ``"bst"`` gives that pool a whole
+    encoder layer with ``ffn`` hidden units (default ``4 * dim``)."""
 
     def __init__(
         self,
@@ -161,6 +214,7 @@ class SeqCTR(nn.Module):
         attention: str = "dot",
         att_hidden: int = 32,
         heads: int = 2,
+        ffn: Optional[int] = None,
     ):
         super().__init__()
         for s, qi in seq_query.items():
@@ -169,7 +223,8 @@ class SeqCTR(nn.Module):
                 f"sequence {s} (dim {dims[s]}) and its query {qi} (dim {dims[qi]})"
         self.seq_query = {int(s): int(qi) for s, qi in seq_query.items()}
         self.num_dense = num_dense
-        assert attention in ("dot", "mlp", "gru", "augru", "self"), attention
+        assert attention in ("dot", "mlp", "gru", "augru", "self", "bst"), \
+            attention
         self.attention = attention
         if attention == "dot":
             self.pool = TargetAttentionPool()
@@ -177,9 +232,11 @@ class SeqCTR(nn.Module):
             self.gru_pools = nn.ModuleDict({
                 str(s): InterestGRUPool(dims[s], attention=attention == "augru")
                 for s in sorted(self.seq_query)})
-        elif attention == "self":
+        elif attention in ("self", "bst"):
             self.sa_pools = nn.ModuleDict({
-                str(s): SelfAttentionPool(dims[s], heads)
+                str(s): SelfAttentionPool(
+                    dims[s], heads,
+                    ffn=None if attention == "self" else ffn or 4 * dims[s])
                 for s in sorted(self.seq_query)})
         else:
             self.act_pools = nn.ModuleDict({
@@ -214,7 +271,7 @@ class SeqCTR(nn.Module):
             if qi is not None:
                 pool = (self.pool if self.attention == "dot"
                         else self.act_pools[str(i)] if self.attention == "mlp"
-                        else self.sa_pools[str(i)] if self.attention == "self"
+                        else self.sa_pools[str(i)] if self.attention in ("self", "bst")
                         else self.gru_pools[str(i)])
                 e = pool(embedding_tensors[qi], e)
             feats.append(e.to(dt))

@@ -413,3 +413,63 @@ def seq_self_attn_reference(
         o = o + x
     o = torch.where(valid.unsqueeze(-1), o, zero)
     return torch.cat([o.to(seq.dtype), seq[..., D:].detach()], dim=-1)
+
+
+# ------------------------- the tail of a transformer block over a raw slot
+
+
+def _layer_norm(v, g, b, eps):
+    mean = v.mean(dim=-1, keepdim=True)
+    c = v - mean
+    return c / torch.sqrt((c * c).mean(dim=-1, keepdim=True) + eps) * g + b
+
+
+def seq_ffn_reference(
+    x: torch.Tensor,  # [B, L, D+1] — the block input, channel D the 0/1 mask
+    a: torch.Tensor,  # [B, L, D+1] — the attention output (its mask is ignored)
+    Wo: torch.Tensor,  # [D, D]
+    bo: torch.Tensor,  # [D]
+    g1: torch.Tensor,  # [D]
+    be1: torch.Tensor,  # [D]
+    W1: torch.Tensor,  # [F, D]
+    b1: torch.Tensor,  # [F]
+    W2: torch.Tensor,  # [D, F]
+    b2: torch.Tensor,  # [D]
+    g2: torch.Tensor,  # [D]
+    be2: torch.Tensor,  # [D]
+    eps: float = 1e-5,
+    operand_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    """Out-projection, add & LayerNorm, feed-forward, add & LayerNorm over the
+    rows of a raw slot's tensor -- what follows the attention in a post-norm
+    ``nn.TransformerEncoderLayer`` with ReLU and no dropout -- in plain torch
+    (not in the reference; csrc/seqffn.hip is the HIP twin).  With Wo16, W1_16,
+    W2_16 the f16 roundings of the matrices:
+
+        valid i:   u_i = LN(x_i + Wo16 a_i + bo; g1, be1)
+                   h_i = relu(W1_16 u_i + b1)
+                   y_i = LN(u_i + W2_16 h_i + b2; g2, be2)
+        invalid i: out_i = 0
+
+    -> [B, L, D+1] in x's dtype with out[..., D] = x[..., D].  LN is over the D
+    channels with the biased variance and ``eps`` inside the square root.  The
+    mask of ``x`` selects: invalid rows of ``x`` and ``a`` are replaced by
+    zeros before any arithmetic and their outputs by zeros after it.  Computes
+    in f32 (f64 for f64 inputs); the f16 rounding of the matrices is part of
+    the definition and straight-through.  ``operand_dtype=torch.float16``
+    additionally rounds, straight-through, the ``u`` that multiplies ``W1`` and
+    the ``h`` that multiplies ``W2`` -- the kernels' MFMA operands, emulated
+    only to size the tests' bounds."""
+    D = x.shape[-1] - 1
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    zero = torch.zeros((), dtype=ct, device=x.device)
+    valid = (x[..., D] != 0).unsqueeze(-1)
+    xv = torch.where(valid, x[..., :D].to(ct), zero)
+    av = torch.where(valid, a[..., :D].to(ct), zero)
+    rnd = _round_f16_st if operand_dtype == torch.float16 else (lambda t: t)
+    Wo, W1, W2 = (_round_f16_st(w.to(ct)) for w in (Wo, W1, W2))
+    u = _layer_norm(xv + av @ Wo.t() + bo.to(ct), g1.to(ct), be1.to(ct), eps)
+    h = torch.relu(rnd(u) @ W1.t() + b1.to(ct))
+    y = _layer_norm(u + rnd(h) @ W2.t() + b2.to(ct), g2.to(ct), be2.to(ct), eps)
+    y = torch.where(valid, y, zero)
+    return torch.cat([y.to(x.dtype), x[..., D:].detach()], dim=-1)
