@@ -909,6 +909,158 @@ __global__ __launch_bounds__(256) void bias_grad_vec_kernel(
     atomicAdd(&db[i], lds_col[i]);
 }
 
+// ---------------------------------------------------------------------------
+// 1-logit head (nn.Linear(K, 1) at the end of a FusedMLP).  The library runs
+// it as three GEMMs with N or K equal to 1; it is ~12 MFLOP over one read of
+// h, so two streaming kernels do it.
+//
+// forward: logit[b] = bf16(sum_k h[b,k] * w[k] + bias), f32 accumulation.
+// A row is shared by G lanes (G = the power of two >= K/8, at most 64), each
+// summing its 8-column vectors, then a xor-shuffle tree over the G lanes.
+__global__ __launch_bounds__(256) void head_fwd_kernel(
+    const short* __restrict__ h, const short* __restrict__ w,
+    const short* __restrict__ bias, short* __restrict__ out, int B, int K,
+    int G) {
+  const int n8 = K / 8;
+  const int lane = threadIdx.x % 64;
+  const int j = lane % G;
+  const int rows_per_wave = 64 / G;
+  const int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+  const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x / 64);
+  const float bval = bf2f(bias[0]);
+  for (int64_t r0 = wave_id * rows_per_wave; r0 < B; r0 += n_waves * rows_per_wave) {
+    const int64_t r = r0 + lane / G;
+    float acc = 0.0f;
+    if (r < B) {
+      for (int v = j; v < n8; v += G) {
+        const bf16x8 hv = *(const bf16x8*)(h + r * K + v * 8);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) acc += bf2f(hv[t]) * bf2f(w[v * 8 + t]);
+      }
+    }
+    for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (r < B && j == 0) out[r] = f2bf(acc + bval);
+  }
+}
+
+// backward, pass 1.  Block `blk` owns rows [blk * rpb, (blk + 1) * rpb).
+// Threads tile (row, 8-column vector): CP = min(K/8, 256) vectors across,
+// RP = 256 / CP rows down; wider K takes several column chunks.  Per element
+// dh = bf16(dz * w) (one product, one rounding); the dz * h products are
+// summed per thread in f32, then over the RP row groups through LDS in row-
+// group order, and stored as the block's partial: part[blk][0..K) for dw and
+// part[blk][K] for db.  No atomics: pass 2 adds the partials in block order,
+// so dw and db do not depend on scheduling.
+__global__ __launch_bounds__(256) void head_bwd_kernel(
+    const short* __restrict__ dz, const short* __restrict__ h,
+    const short* __restrict__ w, short* __restrict__ dh,
+    float* __restrict__ part, int B, int K, int rpb) {
+  __shared__ float red[256 * 8];
+  __shared__ float red_b[256];
+  const int n8 = K / 8;
+  const int CP = n8 < 256 ? n8 : 256;
+  const int RP = 256 / CP;
+  const int tc = threadIdx.x % CP, tr = threadIdx.x / CP;
+  const bool live = tr < RP;
+  const int64_t r_begin = (int64_t)blockIdx.x * rpb;
+  const int64_t r_end = r_begin + rpb < B ? r_begin + rpb : B;
+  float* my_part = part + (int64_t)blockIdx.x * (K + 1);
+  for (int cb = 0; cb < n8; cb += CP) {
+    const int v = cb + tc;
+    const bool on = live && v < n8;
+    float acc[8] = {};
+    float acc_b = 0.0f;
+    if (on) {
+      float wv[8];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) wv[t] = bf2f(w[v * 8 + t]);
+      for (int64_t r = r_begin + tr; r < r_end; r += RP) {
+        const float d = bf2f(dz[r]);
+        const bf16x8 hv = *(const bf16x8*)(h + r * K + v * 8);
+        bf16x8 o;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          o[t] = f2bf(d * wv[t]);
+          acc[t] += d * bf2f(hv[t]);
+        }
+        *(bf16x8*)(dh + r * K + v * 8) = o;
+        if (v == 0) acc_b += d;
+      }
+    }
+    __syncthreads();  // the previous chunk's readers are done with `red`
+#pragma unroll
+    for (int t = 0; t < 8; ++t) red[threadIdx.x * 8 + t] = acc[t];
+    red_b[threadIdx.x] = acc_b;
+    __syncthreads();
+    if (on && tr == 0) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        float s = 0.0f;
+        for (int q = 0; q < RP; ++q) s += red[(q * CP + tc) * 8 + t];
+        my_part[v * 8 + t] = s;
+      }
+      if (v == 0) {
+        float s = 0.0f;
+        for (int q = 0; q < RP; ++q) s += red_b[q * CP];
+        my_part[K] = s;
+      }
+    }
+  }
+}
+
+// backward, pass 2: out[c] = bf16(sum over blocks, in block order, of
+// part[blk][c]) for the K + 1 columns (dw, then db).
+// A block takes 32 columns; its 8 slices of 32 threads each add a contiguous
+// eighth of the blocks' partials in order, and the 8 slice sums are added in
+// slice order: a fixed tree, 1/8 of the dependent loads of one serial chain.
+__global__ __launch_bounds__(256) void head_bwd_reduce_kernel(
+    const float* __restrict__ part, short* __restrict__ dw,
+    short* __restrict__ db, int n_part, int K) {
+  __shared__ float slice_sum[8][32];
+  const int cl = threadIdx.x % 32, sl = threadIdx.x / 32;
+  const int c = blockIdx.x * 32 + cl;
+  const int per = (n_part + 7) / 8;
+  const int p_end = min(n_part, (sl + 1) * per);
+  float s = 0.0f;
+  if (c <= K) {
+    int p = sl * per;
+    for (; p + 8 <= p_end; p += 8) {  // 8 loads in flight, adds in order
+      float t[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) t[q] = part[(int64_t)(p + q) * (K + 1) + c];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) s += t[q];
+    }
+    for (; p < p_end; ++p) s += part[(int64_t)p * (K + 1) + c];
+  }
+  slice_sum[sl][cl] = s;
+  __syncthreads();
+  if (sl != 0 || c > K) return;
+  float tot = 0.0f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) tot += slice_sum[q][cl];
+  if (c < K) dw[c] = f2bf(tot);
+  else db[0] = f2bf(tot);
+}
+
+// out[n][0..Kp) = [w[n][0..K) | zeros]: F.pad's fill + strided copy in one
+// pass.  One thread per 8 output columns (Kp % 8 == 0; source rows may be
+// unaligned, so the reads are scalar).
+__global__ void pad_k_kernel(const short* __restrict__ w,
+                             short* __restrict__ out, int64_t N, int K,
+                             int Kp) {
+  const int kp8 = Kp / 8;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * kp8) return;
+  const int64_t n = i / kp8;
+  const int c0 = (int)(i % kp8) * 8;
+  bf16x8 o;
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+    o[t] = c0 + t < K ? w[n * K + c0 + t] : (short)0;
+  *(bf16x8*)(out + n * Kp + c0) = o;
+}
+
 }  // namespace
 
 // ============================================================ torch bindings
@@ -1303,7 +1455,91 @@ torch::Tensor bce_bwd(torch::Tensor sig, torch::Tensor y, torch::Tensor g) {
   return dz;
 }
 
+// ---- 1-logit head.  h [B, K] bf16 contiguous, w [1, K] (or [K]) bf16, one
+// bf16 bias; K % 8 == 0 and h 16-byte aligned (vector loads of its rows).
+static void head_check(const torch::Tensor& h, const torch::Tensor& w) {
+  TORCH_CHECK(h.is_cuda() && w.is_cuda() && h.device() == w.device());
+  TORCH_CHECK(h.scalar_type() == torch::kBFloat16 &&
+              w.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(h.dim() == 2 && h.is_contiguous() && w.is_contiguous());
+  TORCH_CHECK(h.size(0) > 0 && h.size(0) < (1LL << 31) && h.size(1) > 0 &&
+              h.size(1) % 8 == 0 && w.numel() == h.size(1),
+              "head: needs h [B, K], w [1, K], K % 8 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0,
+              "head: h must be 16-byte aligned");
+}
+
+torch::Tensor head_fwd(torch::Tensor h, torch::Tensor w, torch::Tensor b) {
+  head_check(h, w);
+  TORCH_CHECK(b.is_cuda() && b.device() == h.device() && b.numel() == 1 &&
+              b.scalar_type() == torch::kBFloat16);
+  const int B = (int)h.size(0), K = (int)h.size(1);
+  int G = 1;
+  while (G < 64 && G < K / 8) G *= 2;
+  auto out = torch::empty({B, 1}, h.options());
+  const int rows_per_block = 4 * (64 / G);
+  const int grid = std::min((B + rows_per_block - 1) / rows_per_block, 4096);
+  hipLaunchKernelGGL(head_fwd_kernel, dim3(grid), dim3(256), 0, dcur_stream(),
+                     (const short*)h.data_ptr(), (const short*)w.data_ptr(),
+                     (const short*)b.data_ptr(), (short*)out.data_ptr(), B, K,
+                     G);
+  return out;
+}
+
+std::vector<torch::Tensor> head_bwd(torch::Tensor dz, torch::Tensor h,
+                                    torch::Tensor w) {
+  head_check(h, w);
+  const int B = (int)h.size(0), K = (int)h.size(1);
+  TORCH_CHECK(dz.is_cuda() && dz.device() == h.device() &&
+              dz.scalar_type() == torch::kBFloat16 && dz.is_contiguous() &&
+              dz.numel() == B, "head_bwd: dz must be bf16 [B, 1]");
+  auto dh = torch::empty_like(h);
+  auto dw = torch::empty_like(w);
+  auto db = torch::empty({1}, w.options());
+  // rows per block: whole passes of the block's row groups, <= 512 blocks
+  const int n8 = K / 8;
+  const int RP = 256 / std::min(n8, 256);
+  int rpb = std::max(RP, (B + 511) / 512);
+  rpb = (rpb + RP - 1) / RP * RP;
+  const int grid = (B + rpb - 1) / rpb;
+  auto part = torch::empty(
+      {grid, K + 1},
+      torch::TensorOptions().dtype(torch::kFloat32).device(h.device()));
+  hipLaunchKernelGGL(head_bwd_kernel, dim3(grid), dim3(256), 0, dcur_stream(),
+                     (const short*)dz.data_ptr(), (const short*)h.data_ptr(),
+                     (const short*)w.data_ptr(), (short*)dh.data_ptr(),
+                     part.data_ptr<float>(), B, K, rpb);
+  hipLaunchKernelGGL(head_bwd_reduce_kernel, dim3((K + 1 + 31) / 32), dim3(256),
+                     0, dcur_stream(), part.data_ptr<float>(),
+                     (short*)dw.data_ptr(), (short*)db.data_ptr(), grid, K);
+  return {dh, dw, db};
+}
+
+// zero-padded copy of a 2-D bf16 matrix along its columns, to a multiple of
+// `mult` (itself a multiple of 8); the input itself when nothing is to pad
+torch::Tensor pad_k(torch::Tensor w, int64_t mult) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() &&
+              w.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(mult > 0 && mult % 8 == 0, "pad_k: mult must be a multiple of 8");
+  const int64_t N = w.size(0), K = w.size(1);
+  const int64_t Kp = (K + mult - 1) / mult * mult;
+  if (Kp == K) return w;
+  TORCH_CHECK(Kp < (1LL << 31));
+  auto out = torch::empty({N, Kp}, w.options());
+  const int64_t n_thr = N * (Kp / 8);
+  if (n_thr == 0) return out;
+  hipLaunchKernelGGL(pad_k_kernel, dim3((unsigned)((n_thr + 255) / 256)),
+                     dim3(256), 0, dcur_stream(), (const short*)w.data_ptr(),
+                     (short*)out.data_ptr(), N, (int)K, (int)Kp);
+  return out;
+}
+
 void init_dense(pybind11::module_& m) {
+  m.def("head_fwd", &head_fwd,
+        "1-logit head forward: bf16(h @ w^T + b), f32 accumulation");
+  m.def("head_bwd", &head_bwd,
+        "1-logit head backward -> (dh, dw, db), fixed-order reductions");
+  m.def("pad_k", &pad_k, "zero-pad the columns of a bf16 matrix, one launch");
   m.def("gemm_nt_bias_act", &gemm_nt_bias_act,
         "bf16 MFMA GEMM (A @ B^T) with fused bias+activation");
   m.def("dgrad_drelu_bias", &dgrad_drelu_bias,

@@ -163,9 +163,18 @@ __global__ __launch_bounds__(256) void interact_bwd_mfma_kernel(
 // [S*B, D] (f16, row (f-1)*B + b for feature f>=1).  Staging straight from
 // both skips the [B, F, D] cat + permute + f16->bf16 materialization the
 // model would otherwise run (and their backward copy cascade).
-__global__ __launch_bounds__(256) void interact_fwd_packed_kernel(
+//
+// TOP variants (interact_fwd_top / interact_bwd_top) fold the assembly of the
+// top-MLP input into the same kernels: the forward writes the whole row
+// [x | pair dots | zeros] at pitch ldo = D + P + pad (x is feature row 0 of
+// the LDS image anyway), the backward reads the pair gradients in place at
+// column D of the full-width gradient (pitch ldg, pad columns never read) and
+// adds the gradient's x block to its own dx.  TOP = false is the packed
+// kernel as it was.
+template <bool TOP>
+__device__ __forceinline__ void interact_fwd_packed_body(
     const short* __restrict__ x, const __half* __restrict__ base,
-    short* __restrict__ out, int B, int S, int D, int P) {
+    short* __restrict__ out, int B, int S, int D, int P, int ldo) {
   extern __shared__ short lds[];
   const int F = S + 1;
   const int waves = blockDim.x / 64;
@@ -185,6 +194,15 @@ __global__ __launch_bounds__(256) void interact_fwd_packed_kernel(
       bf16x8i val;
       if (fr == 0) {
         val = *(const bf16x8i*)&x[b * D + c8];
+        if constexpr (TOP) {
+          short* xo = out + b * ldo + c8;
+          if (ldo % 8 == 0) {
+            *(bf16x8i*)xo = val;
+          } else {  // odd pitch: rows are not 16-byte aligned
+#pragma unroll
+            for (int k = 0; k < 8; ++k) xo[k] = val[k];
+          }
+        }
       } else {
         const __half* src = base + ((int64_t)(fr - 1) * B + b) * D + c8;
 #pragma unroll
@@ -192,7 +210,10 @@ __global__ __launch_bounds__(256) void interact_fwd_packed_kernel(
       }
       *(bf16x8i*)&v[fr * LDK + c8] = val;
     }
-    short* dst = out + b * P;
+    short* dst = TOP ? out + b * ldo + D : out + b * P;
+    if constexpr (TOP) {
+      for (int t = P + lane; t < ldo - D; t += 64) dst[t] = 0;
+    }
     for (int ti = 0; ti < T; ++ti) {
       for (int tj = 0; tj <= ti; ++tj) {
         f32x4i acc = {};
@@ -212,10 +233,23 @@ __global__ __launch_bounds__(256) void interact_fwd_packed_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void interact_bwd_packed_kernel(
+__global__ __launch_bounds__(256) void interact_fwd_packed_kernel(
+    const short* __restrict__ x, const __half* __restrict__ base,
+    short* __restrict__ out, int B, int S, int D, int P) {
+  interact_fwd_packed_body<false>(x, base, out, B, S, D, P, P);
+}
+
+__global__ __launch_bounds__(256) void interact_fwd_top_kernel(
+    const short* __restrict__ x, const __half* __restrict__ base,
+    short* __restrict__ out, int B, int S, int D, int P, int ldo) {
+  interact_fwd_packed_body<true>(x, base, out, B, S, D, P, ldo);
+}
+
+template <bool TOP>
+__device__ __forceinline__ void interact_bwd_packed_body(
     const short* __restrict__ g, const short* __restrict__ x,
     const __half* __restrict__ base, short* __restrict__ dx,
-    __half* __restrict__ dbase, int B, int S, int D, int P) {
+    __half* __restrict__ dbase, int B, int S, int D, int P, int ldg) {
   extern __shared__ short lds[];
   const int F = S + 1;
   const int waves = blockDim.x / 64;
@@ -269,7 +303,7 @@ __global__ __launch_bounds__(256) void interact_bwd_packed_kernel(
       }
       *(bf16x8i*)&v[fr * LDV + c8] = row;
     }
-    const short* gp = g + b * P;
+    const short* gp = TOP ? g + b * ldg + D : g + b * P;
     for (int p = lane; p < P; p += 64) {
       int i = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
       while (i * (i - 1) / 2 > p) --i;
@@ -293,7 +327,14 @@ __global__ __launch_bounds__(256) void interact_bwd_packed_kernel(
           for (int r = 0; r < 4; ++r) {
             const int i = ti * 16 + (lane >> 4) * 4 + r;
             if (i == 0) {
-              dx[b * D + d] = if2bf(acc[r]);
+              if constexpr (TOP) {
+                // the two roundings of autograd's bf16 sum of the two
+                // gradients of x: the interaction's own dx, then the sum
+                dx[b * D + d] = if2bf(ibf2f(if2bf(acc[r])) +
+                                      ibf2f(g[b * ldg + d]));
+              } else {
+                dx[b * D + d] = if2bf(acc[r]);
+              }
             } else if (i < F) {
               dbase[((int64_t)(i - 1) * B + b) * D + d] = __float2half(acc[r]);
             }
@@ -302,6 +343,20 @@ __global__ __launch_bounds__(256) void interact_bwd_packed_kernel(
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void interact_bwd_packed_kernel(
+    const short* __restrict__ g, const short* __restrict__ x,
+    const __half* __restrict__ base, short* __restrict__ dx,
+    __half* __restrict__ dbase, int B, int S, int D, int P) {
+  interact_bwd_packed_body<false>(g, x, base, dx, dbase, B, S, D, P, P);
+}
+
+__global__ __launch_bounds__(256) void interact_bwd_top_kernel(
+    const short* __restrict__ g, const short* __restrict__ x,
+    const __half* __restrict__ base, short* __restrict__ dx,
+    __half* __restrict__ dbase, int B, int S, int D, int P, int ldg) {
+  interact_bwd_packed_body<true>(g, x, base, dx, dbase, B, S, D, P, ldg);
 }
 
 // ------------------------------------------------- scalar fallback (legacy)
@@ -524,6 +579,68 @@ std::vector<torch::Tensor> interact_bwd_packed(torch::Tensor g, torch::Tensor x,
   return {dx, dbase};
 }
 
+// Shapes and layouts of the packed operands, shared by the TOP entries.
+static void check_packed(const torch::Tensor& x, const torch::Tensor& base) {
+  TORCH_CHECK(x.is_cuda() && base.is_cuda() && x.device() == base.device());
+  TORCH_CHECK(x.dim() == 2 && base.dim() == 2 && x.size(0) > 0);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
+  TORCH_CHECK(base.scalar_type() == torch::kFloat16 && base.is_contiguous());
+  const int64_t B = x.size(0), D = x.size(1);
+  TORCH_CHECK(D % 8 == 0 && base.size(1) == D && base.size(0) % B == 0 &&
+              base.size(0) >= B);
+}
+
+torch::Tensor interact_fwd_top(torch::Tensor x, torch::Tensor base,
+                               int64_t pad) {
+  check_packed(x, base);
+  TORCH_CHECK(pad >= 0, "interact_fwd_top: negative pad");
+  const int B = (int)x.size(0), D = (int)x.size(1);
+  const int S = (int)(base.size(0) / B);
+  const int F = S + 1;
+  const int P = F * (F - 1) / 2;
+  const int ldo = D + P + (int)pad;
+  auto out = torch::empty({B, ldo}, x.options());
+  const int Fp = ceil16(F), Dk = ceil32(D);
+  const int mfma_shorts = Fp * (Dk + 8);
+  const int waves = pick_waves(mfma_shorts);
+  TORCH_CHECK(waves > 0, "interact_fwd_top: tile exceeds LDS");
+  const int grid = std::min((B + waves - 1) / waves, 8192);
+  hipLaunchKernelGGL(interact_fwd_top_kernel, dim3(grid), dim3(waves * 64),
+                     waves * mfma_shorts * 2, icur_stream(),
+                     (const short*)x.data_ptr(),
+                     (const __half*)base.data_ptr<at::Half>(),
+                     (short*)out.data_ptr(), B, S, D, P, ldo);
+  return out;
+}
+
+std::vector<torch::Tensor> interact_bwd_top(torch::Tensor g, torch::Tensor x,
+                                            torch::Tensor base) {
+  check_packed(x, base);
+  const int B = (int)x.size(0), D = (int)x.size(1);
+  const int S = (int)(base.size(0) / B);
+  const int F = S + 1;
+  const int P = F * (F - 1) / 2;
+  TORCH_CHECK(g.is_cuda() && g.device() == x.device() && g.dim() == 2 &&
+              g.scalar_type() == torch::kBFloat16 && g.is_contiguous());
+  TORCH_CHECK(g.size(0) == B && g.size(1) >= D + P,
+              "interact_bwd_top: gradient narrower than [x | pairs]");
+  const int ldg = (int)g.size(1);
+  auto dx = torch::empty_like(x);
+  auto dbase = torch::empty_like(base);
+  const int Fp = ceil16(F), Fk = ceil32(F), Dp = ceil16(D);
+  const int mfma_shorts = Fp * (Fk + 8) + Fk * (Dp + 8);
+  const int waves = pick_waves(mfma_shorts);
+  TORCH_CHECK(waves > 0, "interact_bwd_top: tile exceeds LDS");
+  const int grid = std::min((B + waves - 1) / waves, 8192);
+  hipLaunchKernelGGL(interact_bwd_top_kernel, dim3(grid), dim3(waves * 64),
+                     waves * mfma_shorts * 2, icur_stream(),
+                     (const short*)g.data_ptr(), (const short*)x.data_ptr(),
+                     (const __half*)base.data_ptr<at::Half>(),
+                     (short*)dx.data_ptr(), (__half*)dbase.data_ptr<at::Half>(),
+                     B, S, D, P, ldg);
+  return {dx, dbase};
+}
+
 // packed variants have no scalar fallback: MFMA images must fit
 bool interact_packed_feasible(int64_t F, int64_t D) {
   if (D % 8 != 0) return false;
@@ -556,4 +673,9 @@ void init_interact(pybind11::module_& m) {
         "interaction from (x bf16 [B,D], slot-major f16 base) directly");
   m.def("interact_bwd_packed", &interact_bwd_packed,
         "packed interaction backward -> (dx, dbase f16)");
+  m.def("interact_fwd_top", &interact_fwd_top,
+        "packed interaction -> the top-MLP input [x | pair dots | zero pad]");
+  m.def("interact_bwd_top", &interact_bwd_top,
+        "backward of interact_fwd_top from the full-width gradient -> "
+        "(summed dx, dbase f16)");
 }

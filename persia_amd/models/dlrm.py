@@ -5,6 +5,7 @@ features, dim=128 — the Criteo shape).  Bottom MLP embeds the dense
 features, a dot-product feature interaction crosses all embedding vectors,
 and a top MLP produces the CTR logit.
 """
+import os
 from typing import List
 
 import torch
@@ -84,15 +85,26 @@ class _InteractFn(torch.autograd.Function):
 class _InteractPackedFn(torch.autograd.Function):
     """Packed-input interaction: consumes the bottom-MLP output x (bf16
     [B, D]) and the engine's slot-major f16 sum base ([S*B, D]) DIRECTLY —
-    no [B, F, D] cat/permute/cast materialization on either pass."""
+    no [B, F, D] cat/permute/cast materialization on either pass.
+
+    ``apply(x, base, pad)`` returns the whole top-MLP input
+    ``[x | pair dots | pad zero columns]`` (interact_fwd_top) and its
+    backward takes the full-width gradient: the pair block is read in place
+    and the x block is added to the interaction's own dx in the kernel, with
+    the two bf16 roundings autograd's sum of the two gradients had.
+    ``apply(x, base)`` returns the pair dots alone (the PA_INTERACT_TOP=0
+    path, assembled by the caller)."""
 
     @staticmethod
-    def forward(ctx, x, base):
+    def forward(ctx, x, base, pad=None):
         from persia_amd.ops import native
 
         x = x.contiguous()
         base = base.contiguous()
         ctx.save_for_backward(x, base)
+        ctx.top = pad is not None
+        if ctx.top:
+            return native().interact_fwd_top(x, base, pad)
         return native().interact_fwd_packed(x, base)
 
     @staticmethod
@@ -100,8 +112,11 @@ class _InteractPackedFn(torch.autograd.Function):
         from persia_amd.ops import native
 
         x, base = ctx.saved_tensors
-        dx, dbase = native().interact_bwd_packed(g, x, base)
-        return dx, dbase
+        if ctx.top:
+            dx, dbase = native().interact_bwd_top(g.contiguous(), x, base)
+        else:
+            dx, dbase = native().interact_bwd_packed(g, x, base)
+        return dx, dbase, None
 
 
 class DotInteraction(nn.Module):
@@ -174,16 +189,21 @@ class DLRM(nn.Module):
                 if native_available() and native().interact_packed_feasible(
                     self.num_sparse + 1, self.dim
                 ):
-                    inter = _InteractPackedFn.apply(x, embedding_tensors)
-                    # build the top input PRE-padded to the fused GEMM's
-                    # K%128 by catting the zero tail here — one cat pass
-                    # instead of cat + a full-width _pad32 copy inside the
-                    # first top layer (zero K-columns hit zero-padded weight
-                    # columns: bit-identical output).  Only the fused top
+                    # the top input is built PRE-padded to the fused GEMM's
+                    # K%128 (zero K-columns hit zero-padded weight columns:
+                    # bit-identical output), which saves a full-width _pad32
+                    # copy inside the first top layer.  Only the fused top
                     # takes a wider input; an eager nn.Linear top would
                     # reject it
-                    k = x.shape[1] + inter.shape[1]
+                    n_f = self.num_sparse + 1
+                    k = x.shape[1] + n_f * (n_f - 1) // 2
                     pad = (-k) % 128 if self.fused else 0
+                    if os.environ.get("PA_INTERACT_TOP", "1") != "0":
+                        # the interaction kernel writes [x | inter | zeros]
+                        top_in = _InteractPackedFn.apply(x, embedding_tensors, pad)
+                        return self.top(top_in).squeeze(1)
+                    # A/B switch: the same input from cat + a zero fill
+                    inter = _InteractPackedFn.apply(x, embedding_tensors)
                     parts = [x, inter]
                     if pad:
                         parts.append(x.new_zeros(B, pad))

@@ -35,6 +35,16 @@ def _pad32(x: torch.Tensor, dim: int, mult: int = 128) -> torch.Tensor:
     pad = (-k) % mult
     if pad == 0:
         return x
+    if (
+        x.is_cuda and x.dim() == 2 and dim == 1 and mult % 8 == 0
+        and x.dtype == torch.bfloat16
+        and not (torch.is_grad_enabled() and x.requires_grad)
+    ):
+        # one launch (csrc/dense.hip pad_k) for F.pad's fill + strided copy:
+        # the ragged-K weights are padded on every step
+        from persia_amd.ops import native
+
+        return native().pad_k(x.contiguous(), mult)
     padding = [0, 0] * (x.dim() - 1 - dim) + [0, pad]
     return F.pad(x, padding)
 
@@ -261,6 +271,49 @@ class FusedLinear(nn.Module):
         return FusedLinearFn.apply(x, self.weight, self.bias, 1 if self.relu else 0)
 
 
+class _HeadFn(torch.autograd.Function):
+    """nn.Linear(K, 1) on bf16 as three streaming kernels (csrc/dense.hip
+    head_fwd / head_bwd) in place of three library GEMMs with N or K = 1 and
+    a bias reduce."""
+
+    @staticmethod
+    def forward(ctx, h, w, b):
+        from persia_amd.ops import native
+
+        ctx.save_for_backward(h, w)
+        return native().head_fwd(h, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        from persia_amd.ops import native
+
+        h, w = ctx.saved_tensors
+        dh, dw, db = native().head_bwd(g.contiguous(), h, w)
+        return dh, dw, db
+
+
+class HeadLinear(nn.Linear):
+    """nn.Linear drop-in (same parameters / state_dict) for a FusedMLP's
+    plain final projection.  A 1-logit bf16 head on the GPU runs the native
+    head kernels; everything else is nn.Linear.  PA_NATIVE_HEAD=0 keeps the
+    library path (A/B switch)."""
+
+    def forward(self, x):
+        import os
+
+        if (
+            x.is_cuda and x.dim() == 2 and x.is_contiguous()
+            and x.dtype == torch.bfloat16
+            and self.out_features == 1 and self.in_features % 8 == 0
+            and self.bias is not None
+            and self.weight.dtype == torch.bfloat16
+            and self.bias.dtype == torch.bfloat16
+            and os.environ.get("PA_NATIVE_HEAD", "1") != "0"
+        ):
+            return _HeadFn.apply(x, self.weight, self.bias)
+        return super().forward(x)
+
+
 class FusedMLP(nn.Module):
     """Stack of FusedLinear layers (+ optional plain final projection when the
     last width isn't a multiple of 32, e.g. the 1-logit head)."""
@@ -274,7 +327,7 @@ class FusedMLP(nn.Module):
             if sizes[i + 1] % 32 == 0:
                 layers.append(FusedLinear(sizes[i], sizes[i + 1], relu=relu))
             else:
-                lin = nn.Linear(sizes[i], sizes[i + 1])
+                lin = HeadLinear(sizes[i], sizes[i + 1])
                 layers.append(lin if not relu else nn.Sequential(lin, nn.ReLU()))
         self.layers = nn.ModuleList(layers)
 
