@@ -2511,6 +2511,7 @@ void init_seqattn(pybind11::module_& m);   // csrc/seqattn.hip
 void init_actunit(pybind11::module_& m);   // csrc/actunit.hip
 void init_seqgru(pybind11::module_& m);    // csrc/seqgru.hip
 void init_seqsa(pybind11::module_& m);     // csrc/seqsa.hip
+void init_seqsal(pybind11::module_& m);    // csrc/seqsal.hip
 void init_seqffn(pybind11::module_& m);    // csrc/seqffn.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2522,6 +2523,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_actunit(m);
   init_seqgru(m);
   init_seqsa(m);
+  init_seqsal(m);
   init_seqffn(m);
   init_checkpoint(m);
   m.def("store_lookup", &store_lookup, "hash-table lookup/insert + gather");

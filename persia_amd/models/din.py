@@ -12,9 +12,9 @@ plain sum, without a softmax (ops/actunit.py, MFMA kernels on the GPU).
 or DIEN's attention-gated AUGRU, whose last state is the pooled vector
 (ops/seqgru.py, a persistent MFMA kernel per direction on the GPU).
 ``SelfAttentionPool`` first lets the rows attend to each other (multi-head
-self-attention, ops/seqsa.py, one MFMA kernel per direction) and then pools
-the result with the target attention above.  ``SeqEncoderLayer`` is the
-whole post-norm transformer block -- that self-attention followed by the
+self-attention, ops/seqsa.py, one MFMA kernel per direction; past 64 rows
+ops/seqsal.py, which streams the keys) and then pools the result with the
+target attention above.  ``SeqEncoderLayer`` is the whole post-norm transformer block -- that self-attention followed by the
 out-projection, add & LayerNorm and the feed-forward (ops/seqffn.py, one more
 MFMA kernel per direction) -- under ``nn.TransformerEncoderLayer``'s parameter
 names."""
@@ -29,6 +29,13 @@ from persia_amd.ops.seqattn import seq_attn_pool
 from persia_amd.ops.seqgru import seq_gru
 from persia_amd.ops.seqffn import seq_ffn
 from persia_amd.ops.seqsa import seq_self_attn
+from persia_amd.ops.seqsal import seq_self_attn_long
+
+
+def _self_attn(seq, *args, **kwargs):
+    """``seq_self_attn`` up to its 64 rows, ``seq_self_attn_long`` past them."""
+    fn = seq_self_attn if seq.shape[1] <= 64 else seq_self_attn_long
+    return fn(seq, *args, **kwargs)
 
 
 class TargetAttentionPool(nn.Module):
@@ -110,8 +117,8 @@ class SelfAttentionLayer(nn.Module):
         self.heads, self.causal = heads, causal
 
     def forward(self, seq, Wqkv, bqkv) -> torch.Tensor:
-        return seq_self_attn(seq, Wqkv, bqkv, self.heads, self.causal,
-                             residual=True)
+        return _self_attn(seq, Wqkv, bqkv, self.heads, self.causal,
+                          residual=True)
 
 
 class _InProj(nn.Module):
@@ -145,8 +152,8 @@ class SeqEncoderLayer(nn.Module):
 
     def forward(self, seq: torch.Tensor) -> torch.Tensor:
         sa, n1, n2 = self.self_attn, self.norm1, self.norm2
-        a = seq_self_attn(seq, sa.in_proj_weight, sa.in_proj_bias, self.heads,
-                          self.causal, residual=False)
+        a = _self_attn(seq, sa.in_proj_weight, sa.in_proj_bias, self.heads,
+                       self.causal, residual=False)
         return seq_ffn(seq, a, sa.out_proj.weight, sa.out_proj.bias, n1.weight,
                        n1.bias, self.linear1.weight, self.linear1.bias,
                        self.linear2.weight, self.linear2.bias, n2.weight,
