@@ -2508,6 +2508,7 @@ void init_engine(pybind11::module_& m);    // csrc/engine.cpp
 void init_interact(pybind11::module_& m);  // csrc/interact.hip
 void init_checkpoint(pybind11::module_& m);  // csrc/checkpoint.hip
 void init_seqattn(pybind11::module_& m);   // csrc/seqattn.hip
+void init_seqattnl(pybind11::module_& m);  // csrc/seqattnl.hip
 void init_actunit(pybind11::module_& m);   // csrc/actunit.hip
 void init_seqgru(pybind11::module_& m);    // csrc/seqgru.hip
 void init_seqsa(pybind11::module_& m);     // csrc/seqsa.hip
@@ -2520,6 +2521,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_engine(m);
   init_interact(m);
   init_seqattn(m);
+  init_seqattnl(m);
   init_actunit(m);
   init_seqgru(m);
   init_seqsa(m);

@@ -14,7 +14,8 @@ or DIEN's attention-gated AUGRU, whose last state is the pooled vector
 ``SelfAttentionPool`` first lets the rows attend to each other (multi-head
 self-attention, ops/seqsa.py, one MFMA kernel per direction; past 64 rows
 ops/seqsal.py, which streams the keys) and then pools the result with the
-target attention above.  ``SeqEncoderLayer`` is the whole post-norm transformer block -- that self-attention followed by the
+target attention above.  Samples too long for the pooling kernel's LDS image
+are pooled by ops/seqattnl.py, which streams the rows.  ``SeqEncoderLayer`` is the whole post-norm transformer block -- that self-attention followed by the
 out-projection, add & LayerNorm and the feed-forward (ops/seqffn.py, one more
 MFMA kernel per direction) -- under ``nn.TransformerEncoderLayer``'s parameter
 names."""
@@ -24,8 +25,10 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
+from persia_amd.ops import native_available
 from persia_amd.ops.actunit import act_unit_pool
 from persia_amd.ops.seqattn import seq_attn_pool
+from persia_amd.ops.seqattnl import prefers_long, seq_attn_pool_long
 from persia_amd.ops.seqgru import seq_gru
 from persia_amd.ops.seqffn import seq_ffn
 from persia_amd.ops.seqsa import seq_self_attn
@@ -38,6 +41,14 @@ def _self_attn(seq, *args, **kwargs):
     return fn(seq, *args, **kwargs)
 
 
+def _attn_pool(q, seq, scale=None):
+    """``seq_attn_pool`` where its kernel takes the sample, on the GPU
+    ``seq_attn_pool_long`` past that (``ops.seqattnl.prefers_long``)."""
+    long = (q.is_cuda and seq.is_cuda and q.dim() == 2 and seq.dim() == 3
+            and native_available() and prefers_long(seq.shape[1], q.shape[1]))
+    return (seq_attn_pool_long if long else seq_attn_pool)(q, seq, scale)
+
+
 class TargetAttentionPool(nn.Module):
     """forward(query [B, D], seq [B, L, D+1]) -> [B, D]; scale 1/sqrt(D)
     unless given."""
@@ -47,7 +58,7 @@ class TargetAttentionPool(nn.Module):
         self.scale = scale
 
     def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
-        return seq_attn_pool(query, seq, self.scale)
+        return _attn_pool(query, seq, self.scale)
 
 
 class ActivationUnitPool(nn.Module):
@@ -186,8 +197,8 @@ class SelfAttentionPool(nn.Module):
 
     def forward(self, query: torch.Tensor, seq: torch.Tensor) -> torch.Tensor:
         if hasattr(self, "encoder"):
-            return seq_attn_pool(query, self.encoder(seq))
-        return seq_attn_pool(
+            return _attn_pool(query, self.encoder(seq))
+        return _attn_pool(
             query, self.layer(seq, self.in_proj_weight, self.in_proj_bias))
 
 

@@ -20,6 +20,7 @@ ext = CUDAExtension(
         "persia_amd/csrc/dense.hip",
         "persia_amd/csrc/interact.hip",
         "persia_amd/csrc/seqattn.hip",
+        "persia_amd/csrc/seqattnl.hip",
         "persia_amd/csrc/actunit.hip",
         "persia_amd/csrc/seqgru.hip",
         "persia_amd/csrc/seqsa.hip",
