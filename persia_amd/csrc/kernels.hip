@@ -2514,6 +2514,7 @@ void init_seqgru(pybind11::module_& m);    // csrc/seqgru.hip
 void init_seqsa(pybind11::module_& m);     // csrc/seqsa.hip
 void init_seqsal(pybind11::module_& m);    // csrc/seqsal.hip
 void init_seqffn(pybind11::module_& m);    // csrc/seqffn.hip
+void init_cross(pybind11::module_& m);     // csrc/cross.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "persia_amd HIP kernels (gfx950)";
@@ -2527,6 +2528,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_seqsa(m);
   init_seqsal(m);
   init_seqffn(m);
+  init_cross(m);
   init_checkpoint(m);
   m.def("store_lookup", &store_lookup, "hash-table lookup/insert + gather");
   m.def("store_probe", &store_probe, "probe-only (spill-tier miss detection)");

@@ -44,9 +44,16 @@ class DCNv2(nn.Module):
         deep: List[int] = (512, 256, 128),
         cross_rank: int = 256,
         fused: bool = False,
+        fused_cross: bool = False,
     ):
         super().__init__()
         in_dim = num_dense + num_sparse * dim
+        # fused_cross: the whole low-rank cross stack as one autograd node on
+        # the csrc/cross.hip kernels (ops.cross.cross_stack) over the same
+        # modules and parameter names; full rank stays on the per-layer path
+        assert not fused_cross or (fused and 0 < cross_rank < in_dim), \
+            "fused_cross needs fused=True and 0 < cross_rank < in_dim"
+        self.fused_cross = fused_cross
         # fused path: pad the wide feature vector to a multiple of 32 so the
         # MFMA kernels' K/N constraints hold end-to-end (zero features are
         # inert through cross layers, deep tower and head)
@@ -93,8 +100,18 @@ class DCNv2(nn.Module):
             )
         if self.pad:
             x0 = torch.nn.functional.pad(x0, (0, self.pad))
-        xl = x0
-        for layer in self.cross:
-            xl = layer(x0, xl)
+        if self.fused_cross:
+            from persia_amd.ops.cross import cross_stack
+
+            xl = cross_stack(
+                x0.contiguous(),
+                [layer.v.weight for layer in self.cross],
+                [layer.u.weight for layer in self.cross],
+                [layer.u.bias for layer in self.cross],
+            )
+        else:
+            xl = x0
+            for layer in self.cross:
+                xl = layer(x0, xl)
         d = self.deep(x0)
         return self.head(torch.cat([xl, d.to(xl.dtype)], dim=1)).squeeze(1).float()

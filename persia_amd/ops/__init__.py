@@ -46,3 +46,7 @@ def native_available() -> bool:
 def require_native_on_gpu(device: torch.device):
     if device.type == "cuda":
         native()  # raises with a clear message if missing
+
+
+from persia_amd.ops.cross import cross_stack  # noqa: E402,F401
+from persia_amd.ops.reference import cross_stack_reference  # noqa: E402,F401

@@ -473,3 +473,19 @@ def seq_ffn_reference(
     y = _layer_norm(u + rnd(h) @ W2.t() + b2.to(ct), g2.to(ct), be2.to(ct), eps)
     y = torch.where(valid, y, zero)
     return torch.cat([y.to(x.dtype), x[..., D:].detach()], dim=-1)
+
+
+# ------------------------------------------ the DCN-v2 low-rank cross stack
+
+
+def cross_stack_reference(x0, Vs, Us, bs):
+    """A stack of DCN-v2 low-rank cross layers in plain torch (the HIP twin is
+    csrc/cross.hip): with x_0 = x0 [B, D], V_l [r, D], U_l [D, r], b_l [D],
+
+        x_{l+1} = x0 * (x_l V_l^T U_l^T + b_l) + x_l
+
+    -> x_n, in the tensors' dtype, differentiable in every argument."""
+    xl = x0
+    for V, U, b in zip(Vs, Us, bs):
+        xl = x0 * (xl @ V.t() @ U.t() + b) + xl
+    return xl

@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "persia_amd/csrc/seqsa.hip",
         "persia_amd/csrc/seqsal.hip",
         "persia_amd/csrc/seqffn.hip",
+        "persia_amd/csrc/cross.hip",
         "persia_amd/csrc/checkpoint.hip",
         "persia_amd/csrc/engine.cpp",
     ],
